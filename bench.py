@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the neural-process hot path on MI355X (see DESIGN.md section "Measurement").
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 Default (= ``--config c2``): a step = forward + loss + backward + (N > 1: bucketed RCCL gradient
 all-reduce) + Adam on one synthetic batch of the BASELINE.json config-2 workload: AttnCNP
@@ -10,6 +10,14 @@ all-reduce) + Adam on one synthetic batch of the BASELINE.json config-2 workload
 GPU; ``c4`` = the data-parallel configuration, 1024 tasks per GPU (8192 global at N = 8), fp32 or
 ``--dtype bf16``; ``c5`` = decode only (r = 512 decoder, 4096 targets, 512 waveforms per GPU).
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline (``value``, ``ms_per_step``).  ``--full`` adds
+what takes runs of its own after the timed region: the same K steps launched eagerly with the phases of the step timed (the
+exchange figures at N > 1), the instrumented per-launch pass behind ``roofline`` / ``config.kernels`` and the CPU baseline
+(``--no-roofline`` / ``--no-cpu-baseline`` leave parts of it out).  ``--dump-outputs DIR`` writes what the last timed step
+returned to its caller as ``DIR/<name>.npy`` (float32; at most 64 MB in all, larger outputs as a fixed seeded sample): the
+train step's loss, the flat parameters after its Adam update and its flat gradient; the decode's loc and scale.  The inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: either launch the ranks yourself (``python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...``) or call ``python bench.py --gpus N`` bare: the process then starts N ranks
@@ -77,8 +85,13 @@ def parse_args(argv=None):
                          "eagerly with the bucketed all-reduce overlapped with the backward pass (the N > 1 default: with the input "
                          "range check kept on the device an eagerly launched step costs what a replayed one does -- 6.39 against "
                          "6.36 ms at N = 1 -- and hides the exchange)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the eager comparison with the exchange / backward phases, the per-launch "
+                         "roofline pass and the CPU baseline (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: leave out the per-launch roofline pass")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args(argv)
     if args.config is None:
         if args.workload == "decode":
@@ -313,6 +326,35 @@ def timed_region(step, n_steps: int, sync):
     return elapsed, spread, last
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # array data of --dump-outputs: under 64 MB in all with the .npy headers
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write ``{name: tensor}`` as ``out_dir/<name>.npy`` (float64 stays float64, everything else float32).  Over the
+    budget, each array keeps its share of it as a fixed sample: flat indices drawn without replacement by a generator seeded
+    with 0, in ascending order -- the same elements from run to run.  Returns what was written, for the JSON line."""
+    import numpy as np
+    import torch
+
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        info = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": None}
+        keep = int(DUMP_BUDGET_BYTES * a.nbytes / total) // a.itemsize if total > DUMP_BUDGET_BYTES else a.size
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            info["sampled"] = f"{keep} of {a.size} elements: flat indices drawn with seed 0, ascending"
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = info
+    return {"dir": out_dir, "arrays": written}
+
+
 def profile_launches(step, n_prof: int, rank: int, sync, CH):
     """Instrumented pass after the timed region: HIP events around every kernel launch on the launch
     stream (rank 0); every rank runs the steps because a train step contains the gradient all-reduce.
@@ -459,24 +501,33 @@ def main_decode(args, rank, world, dev, sync):
     def step(_i=0):
         with torch.no_grad():
             p = model.decode(Xt, R)
-        return p.base_dist.loc
+        return p.base_dist.loc, p.base_dist.scale
 
+    # set-up: one step with its launches listed by name (no timing is read) -- the line's dtype names the kernel the decode runs
+    CH.PROFILE = []
+    step()
+    sync()
+    launched = {rec[0] for rec in CH.PROFILE}
+    CH.PROFILE = None
     for _ in range(args.warmup):
         step()
-    elapsed, spread, loc = timed_region(step, args.steps, sync)
+    elapsed, spread, (loc, scale) = timed_region(step, args.steps, sync)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * B * T * args.steps / elapsed
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = dump_outputs(args.dump_outputs, {"loc": loc, "scale": scale})
     roofline, kernels = None, {}
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         agg, kernels, launches = profile_launches(step, 2, rank, sync, CH)
         if rank == 0:
             SPLIT_KERNELS.update(("mlp_x6_kernel", "x6_program_kernel"))
             roofline = roofline_of(agg, "fp32", "c5", args.preset, 2, elapsed / args.steps * 1e3, launches)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_decode(r, L, T)
     if rank == 0:
         flop_pt = FLOP_PER_PT_DECODE_R512_L4 if (r, L) == (512, 4) else None
@@ -486,7 +537,7 @@ def main_decode(args, rank, world, dev, sync):
             "ms_per_step_spread": spread,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": ("f32 (fp32 operands as three exact bf16 terms, six v_mfma_f32_16x16x32_bf16 per product group, f32 accumulation "
-                      "-- f32 results, DESIGN.md 3.1 / 3.2)" if "x6_program_kernel" in kernels else "f32"),
+                      "-- f32 results, DESIGN.md 3.1 / 3.2)" if "x6_program_kernel" in launched else "f32"),
             "data": "synthetic",
             "config": {"workload": f"BASELINE config 5: decode(X_trgt_enc, R_trgt) only, {r}-wide {L}-layer decoder, {T} target "
                                    f"points per waveform, {B} waveforms per GPU, fp32, encoder outputs resident in HBM "
@@ -494,7 +545,7 @@ def main_decode(args, rank, world, dev, sync):
                        "tasks_per_gpu": B, "global_tasks": B * world, "target_points": T, "r_dim": r,
                        "parallelism": f"replicas x{world} (no collective)", "checksum_loc": float(loc.double().sum().item()),
                        "decode_tflops_algorithmic": (value * flop_pt * 1e-12) if flop_pt else None, "kernels": kernels},
-            "roofline": roofline, "cpu_baseline": cpu}))
+            "roofline": roofline, "cpu_baseline": cpu, **({"outputs": outputs} if outputs else {})}))
 
 
 def main_train(args, rank, world, dev, sync, rehearsal):
@@ -535,9 +586,14 @@ def main_train(args, rank, world, dev, sync, rehearsal):
     value = world * B * T * args.steps / elapsed
     loss_val = float(loss.item())
     trainer.check_inputs()  # (graph mode: the range check's verdict, deferred to this sync point)
-    # beside the headline: (1) N > 1, graph mode: the all-reduce between the two replayed graphs, timed by HIP events over
-    # another K steps; (2) the same K steps launched eagerly (bucketed all-reduce overlapped with the backward pass) with the
-    # phases of the step timed -- how much of the exchange the backward pass hides there, and what the host costs
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step holds after it: the loss, and the model's flat parameters after Adam with the gradient
+        outputs = dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "params": trainer.flat.flat,
+                                                   "grad": trainer.flat.flat.grad})
+    # beside the headline (--full): (1) N > 1, graph mode: the all-reduce between the two replayed graphs, timed by HIP events
+    # over another K steps; (2) the same K steps launched eagerly (bucketed all-reduce overlapped with the backward pass) with
+    # the phases of the step timed -- how much of the exchange the backward pass hides there, and what the host costs
     def timed_with_phases(fn):
         trainer.phase_events = []
         el, _, _ = timed_region(fn, args.steps, sync)
@@ -550,15 +606,16 @@ def main_train(args, rank, world, dev, sync, rehearsal):
         return el / args.steps * 1e3, ph
 
     phases = {}
-    if use_graph and world > 1:
-        _, phases = timed_with_phases(step)
-    ms_eager, phases_eager = timed_with_phases(lambda i: trainer.step(batches[i % len(batches)], eager=True))
-    if not use_graph:
-        phases = phases_eager
-    trainer.check_inputs()
+    if args.full:
+        if use_graph and world > 1:
+            _, phases = timed_with_phases(step)
+        ms_eager, phases_eager = timed_with_phases(lambda i: trainer.step(batches[i % len(batches)], eager=True))
+        if not use_graph:
+            phases = phases_eager
+        trainer.check_inputs()
 
     roofline, kernels = None, {}
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # (HIP events per launch cannot be recorded inside a graph replay: the instrumented steps run eagerly)
         agg, kernels, launches = profile_launches(lambda i: trainer.step(batches[i % len(batches)], eager=True), 3, rank, sync, CH)
         if rank == 0:
@@ -571,7 +628,7 @@ def main_train(args, rank, world, dev, sync, rehearsal):
                                    elapsed / args.steps * 1e3, launches)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.model, args.r, args.layers, C, T)
 
     if rank == 0:
@@ -586,13 +643,18 @@ def main_train(args, rank, world, dev, sync, rehearsal):
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_step_spread": spread,
-            "allreduce_ms_exposed": phases.get("allreduce_ms_exposed") if world > 1 else 0.0,
-            "backward_ms": phases.get("backward_ms"),
-            "eager": {"ms_per_step": ms_eager, "backward_ms": phases_eager.get("backward_ms"),
-                      "allreduce_ms_exposed": phases_eager.get("allreduce_ms_exposed") if world > 1 else 0.0,
-                      "note": "the same steps launched eagerly (Trainer(use_graph=False, defer_input_check=True)): bucketed "
-                              "all-reduce overlapped with the backward pass -- what N > 1 runs unless --dp-graph; the N = 1 "
-                              "headline replays the step from a HIP graph"},
+        }
+        if args.full:
+            line.update({
+                "allreduce_ms_exposed": phases.get("allreduce_ms_exposed") if world > 1 else 0.0,
+                "backward_ms": phases.get("backward_ms"),
+                "eager": {"ms_per_step": ms_eager, "backward_ms": phases_eager.get("backward_ms"),
+                          "allreduce_ms_exposed": phases_eager.get("allreduce_ms_exposed") if world > 1 else 0.0,
+                          "note": "the same steps launched eagerly (Trainer(use_graph=False, defer_input_check=True)): bucketed "
+                                  "all-reduce overlapped with the backward pass -- what N > 1 runs unless --dp-graph; the N = 1 "
+                                  "headline replays the step from a HIP graph"},
+            })
+        line.update({
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -614,7 +676,9 @@ def main_train(args, rank, world, dev, sync, rehearsal):
             },
             "roofline": roofline,
             "cpu_baseline": cpu,
-        }
+        })
+        if outputs:
+            line["outputs"] = outputs
         print(json.dumps(line))
 
 

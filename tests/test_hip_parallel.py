@@ -101,7 +101,7 @@ def test_bench_two_rank_line_carries_the_exchange_figures(dp_graph):
     env = dict(os.environ, NPF_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--config", "c4", "--batch", "16",
-           "--steps", "3", "--warmup", "1", "--no-roofline"] + (["--dp-graph"] if dp_graph else [])
+           "--steps", "3", "--warmup", "1", "--full", "--no-roofline"] + (["--dp-graph"] if dp_graph else [])
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

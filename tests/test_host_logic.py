@@ -404,21 +404,38 @@ def test_optimizer_state_is_interchangeable_with_per_parameter_adam():
         torch.testing.assert_close(a, b, rtol=1e-6, atol=1e-7, msg=k)
 
 
-def test_shipped_skorch_optimizer_state_loads(tmp_path):
-    """The ``optimizer.pt`` the reference ships next to its pretrained CNP (written by skorch's Checkpoint) loads into
-    the Trainer: every parameter's moments land in its slice of the flat buffers."""
-    import shutil
+def _write_skorch_checkpoint(dirname):
+    """``params.pt`` / ``optimizer.pt`` in the layout skorch's Checkpoint wrote next to the reference's pretrained CNP
+    (results/pretrained/RBF_Kernel/CNP/run_0): the model's state_dict, and the state_dict of a per-parameter Adam after a
+    few steps as torch < 1.12 saved it -- state and param group keyed by ``id()`` of the parameters, ``step`` a plain int."""
+    g = torch.Generator().manual_seed(7)
+    model = _cnp_like_the_shipped_checkpoint()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    for _ in range(3):
+        for p in model.parameters():
+            p.grad = torch.randn(p.shape, generator=g)
+        opt.step()
+    sd = opt.state_dict()
+    ids = [id(p) for p in model.parameters()]
+    sd["state"] = {ids[i]: {"step": int(s["step"]), "exp_avg": s["exp_avg"], "exp_avg_sq": s["exp_avg_sq"]}
+                   for i, s in sd["state"].items()}
+    sd["param_groups"][0]["params"] = ids
+    torch.save(model.state_dict(), os.path.join(dirname, "params.pt"))
+    torch.save(sd, os.path.join(dirname, "optimizer.pt"))
+    return model
 
+
+def test_shipped_skorch_optimizer_state_loads(tmp_path):
+    """An ``optimizer.pt`` in the layout the reference ships next to its pretrained CNP (written by skorch's Checkpoint)
+    loads into the Trainer: every parameter's moments land in its slice of the flat buffers."""
     import npf_gwwaveform_amd as A
     from npf_gwwaveform_amd.train import Trainer
 
-    src = "/root/reference/results/pretrained/RBF_Kernel/CNP/run_0"
-    if not os.path.exists(os.path.join(src, "optimizer.pt")):
-        pytest.skip("the reference checkout is not present on this box")
-    for f in ("params.pt", "optimizer.pt"):
-        shutil.copy(os.path.join(src, f), tmp_path / f)
+    saved = _write_skorch_checkpoint(str(tmp_path))
     t = Trainer(_cnp_like_the_shipped_checkpoint(), A.CNPFLoss(), lr=1e-3, world=1)
     t.load_checkpoint(str(tmp_path))
+    for (k, a), (_, b) in zip(saved.state_dict().items(), t.model.state_dict().items()):
+        assert torch.equal(a, b), k
     sd = torch.load(tmp_path / "optimizer.pt", map_location="cpu", weights_only=True)
     st = t.opt.state[t.flat.flat]
     for pid, p, o, n in zip(sd["param_groups"][0]["params"], t.flat.params, t.flat.offsets, t.flat.sizes):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Development aid: print the per-launch table of a bench.py JSON line (file argument)."""
+"""Development aid: print the per-launch table of a `bench.py --full` JSON line (file argument)."""
 import json
 import signal
 import sys

@@ -14,8 +14,8 @@ names = []
 for so in sorted(glob.glob(os.path.join(ROOT, "tools", "variants", "*.so"))):
     name = os.path.basename(so)[:-3]
     env = dict(os.environ, NPF_HIP_LIB=so)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "6", "--warmup", "2",
-                          *sys.argv[1:]], env=env, capture_output=True, text=True)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "6",
+                          "--warmup", "2", *sys.argv[1:]], env=env, capture_output=True, text=True)
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     if res.returncode != 0 or not line:
         print(name, "FAILED", res.stderr[-500:])

@@ -4,8 +4,8 @@
 set -e
 OUT=${1:-gpurun_out/pmc_wait}; shift || true
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; cd "$ROOT"; export TMPDIR=/tmp; mkdir -p $OUT
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES -d $OUT/a --output-format csv -- python3 bench.py --no-cpu-baseline --no-roofline --steps 3 --warmup 1 "$@" > $OUT/a.log 2>&1
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES -d $OUT/b --output-format csv -- python3 bench.py --no-cpu-baseline --no-roofline --steps 3 --warmup 1 "$@" > $OUT/b.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES -d $OUT/a --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-roofline --steps 3 --warmup 1 "$@" > $OUT/a.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES -d $OUT/b --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-roofline --steps 3 --warmup 1 "$@" > $OUT/b.log 2>&1
 python3 - $OUT <<'PY'
 import csv, glob, sys, collections
 out = sys.argv[1]

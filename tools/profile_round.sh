@@ -8,7 +8,7 @@ set -e
 TAG=${1:-r02}
 CFG=${2:-c2}
 shift 2 || true
-ARGS="--config $CFG $@"
+ARGS="--full --config $CFG $@"
 NAME=${TAG}_${CFG}
 OUT=gpurun_out/prof_$NAME
 case " $ARGS " in *" --gpus "*) echo "profile_round.sh profiles the single-GPU run only (bench.py --gpus N spawns ranks: not under rocprofv3)"; exit 2;; esac
