@@ -1,4 +1,5 @@
 """Helpers shared by the tests: build this package's models for a golden case."""
+import contextlib
 import warnings
 from functools import partial
 
@@ -71,3 +72,74 @@ def assert_close(got, ref, tol=1e-5, what=""):
     err = np.abs(got - ref).max()
     assert np.isfinite(got).all(), f"{what}: non-finite values"
     assert err <= tol * m, f"{what}: max|d|={err:.3e} > {tol:.0e} * max|ref|={m:.3e}"
+
+
+class _RecordingLib:
+    """Stands in for the loaded ``libnpf_hip.so`` handle: every ``npf_*`` attribute fetched through it is wrapped so that a call
+    counts under its name before it runs.  Everything else passes through."""
+
+    def __init__(self, lib, counts):
+        self._real, self._counts = lib, counts
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+        if not name.startswith("npf_"):
+            return fn
+        counts = self._counts
+
+        def call(*args):
+            counts[name] = counts.get(name, 0) + 1
+            return fn(*args)
+
+        return call
+
+
+class LaunchWitness:
+    """What a block of code launched: ``calls`` maps each C-ABI entry point (``npf_chain_run``, ``npf_x6_run_ex``, ...) to the
+    number of times it was called, ``spied`` each spied Python function (``"module.attr"``) likewise."""
+
+    def __init__(self):
+        self.calls, self.spied = {}, {}
+
+    def __getitem__(self, name):
+        return self.calls.get(name, 0) if name.startswith("npf_") else self.spied.get(name, 0)
+
+    def reset(self):
+        self.calls.clear()
+        self.spied.clear()
+
+    def __repr__(self):
+        return f"LaunchWitness({dict(sorted(self.calls.items()))}, spied={dict(sorted(self.spied.items()))})"
+
+
+@contextlib.contextmanager
+def launch_witness(spy=()):
+    """Record every entry point of the HIP library called inside the block.  Every launch of the package goes through
+    ``_lib.load().npf_xxx(...)`` at call time, so swapping the cached handle for a recording proxy sees all of them; the real
+    handle is put back on exit, also when the block raises.  ``spy``: names ``"module.attr"`` of functions of the package
+    (looked up at call time by their callers) whose calls are counted too, e.g. ``"attention_long.long_scaledot_attention"``."""
+    import importlib
+
+    from npf_gwwaveform_amd import _lib as L
+
+    w = LaunchWitness()
+    real = L.load()
+    patched = []
+    try:
+        for name in spy:
+            mod_name, attr = name.rsplit(".", 1)
+            mod = importlib.import_module(f"npf_gwwaveform_amd.{mod_name}")
+            orig = getattr(mod, attr)
+
+            def counted(*a, _orig=orig, _name=name, **kw):
+                w.spied[_name] = w.spied.get(_name, 0) + 1
+                return _orig(*a, **kw)
+
+            patched.append((mod, attr, orig))
+            setattr(mod, attr, counted)
+        L._lib = _RecordingLib(real, w.calls)
+        yield w
+    finally:
+        L._lib = real
+        for mod, attr, orig in reversed(patched):
+            setattr(mod, attr, orig)

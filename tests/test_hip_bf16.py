@@ -61,6 +61,9 @@ CASES.update({k: SWEEP[k] for k in ("cnp_r48", "cnp_r100_dx3_dy1", "cnp_r200_L1"
                                     "attncnp_c2_full", "attnlnp_c2_full",
                                     # residual layers on the ring pipeline, kq width != value width
                                     "attncnp_r256_res", "attncnp_xt128_r256")})
+# r = 256 on both sides of the fused target side's switch (C = 128 / 129: chain attention / b16 program) and past one score row
+# (C = 257: the attention in fp32, blocked, the decoder in bf16)
+CASES.update({f"attncnp_r256_c{C}": dict(kind="AttnCNP", r=256, L_xy=2, L_dec=2, dx=1, dy=2, B=2, C=C, T=70) for C in (128, 129, 257)})
 
 
 def _hip_bf16(case, inp, params, trace=None):

@@ -124,3 +124,28 @@ def test_dot_attender_long_context_matches_torch():
     assert_close(out, ref, what="context vectors")
     for name, a, b in zip(("dK", "dQ", "dV"), dev_in, ref_in):
         assert_close(a.grad, b.grad, tol=2e-5, what=name)
+
+
+@pytest.mark.parametrize("regime", ["large", "one_key", "equal"])
+@pytest.mark.parametrize("C", [128, 129, 256, 257])
+def test_dot_attender_score_regimes(regime, C):
+    """DotAttender.forward at d = 256 on both sides of the one-score-row limit (chain path up to 256 keys, blocked softmax of
+    attention_long.py beyond) with large scores (max q.k / sqrt(d) about 40), one key that dominates every query, and all keys
+    equal -- forward and the three gradients against float64.  Those float64 results are ill-conditioned in the inputs' rounding,
+    so the gate is max(the long-context test's gate, 4 x the error of the same formula evaluated in fp32 torch)
+    (test_hip_mha.assert_gated)."""
+    import npf_gwwaveform_amd as A
+    from test_hip_mha import _regime, assert_gated, attention_and_grads
+
+    B, T, d = 2, 70, 256
+    g = torch.Generator().manual_seed(C)
+    Q, K, V = _regime(regime, B, C, T, d, 1, g)
+    dO = torch.randn(B, T, d, generator=g)
+    r64, r32 = (attention_and_grads(Q, K, V, dO, 1, dt) for dt in (torch.float64, torch.float32))
+    att = A.get_attender("scaledot", d, d, d)
+    dev_in = [t.to(DEV).requires_grad_(True) for t in (K, Q, V)]
+    out = att(*dev_in)
+    out.backward(dO.to(DEV))
+    for i, (name, got, tol) in enumerate((("context vectors", out, 1e-5), ("dQ", dev_in[1].grad, 2e-5), ("dK", dev_in[0].grad, 2e-5),
+                                          ("dV", dev_in[2].grad, 2e-5))):
+        assert_gated(got, r64[i], r32[i], tol, f"{regime} {name}")
