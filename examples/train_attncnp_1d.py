@@ -40,9 +40,14 @@ def main():
     ap.add_argument("--r", type=int, default=128)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph (fixed batch shapes)")
+    ap.add_argument("--per-task-contexts", action="store_true",
+                    help="every task draws its own context size; the batch comes padded with the sizes as n_cntxt and the "
+                         "step is replayed from ONE captured graph (implies --graph)")
     ap.add_argument("--out", default="/tmp/npf_example_ckpt")
     args = ap.parse_args()
     dev = "cuda:0"
+    if args.per_task_contexts:
+        args.graph = True
     A.set_compute_dtype(args.dtype)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -53,12 +58,13 @@ def main():
     trainer.set_lr_decay(10, max(args.steps // 50, 1))
     # (a captured graph needs fixed shapes: a fixed number of context points per batch in that mode)
     n_ctx = dict(a=32, b=32) if args.graph else dict(a=0.1, b=0.5)
+    if args.per_task_contexts:  # (sizes as data: the context tensors keep the shape of the largest size)
+        n_ctx = dict(a=0.1, b=0.5, is_per_task=True)
     split = A.CntxtTrgtGetter(contexts_getter=A.GetRandomIndcs(**n_ctx), targets_getter=A.get_all_indcs)
     t0 = time.perf_counter()
     for step in range(args.steps):
         X, Y = functions(args.tasks, args.points, dev, seed=step)
-        Xc, Yc, Xt, Yt = split(X, Y)
-        loss = trainer.step(dict(X_cntxt=Xc, Y_cntxt=Yc, X_trgt=Xt, Y_trgt=Yt))
+        loss = trainer.step(split.batch(X, Y))
         if (step + 1) % 50 == 0:
             print(f"step {step + 1:5d}  loss/task {loss.item():9.3f}  lr {trainer.end_epoch():.2e}  "
                   f"{(step + 1) * args.tasks * args.points / (time.perf_counter() - t0):,.0f} target-points/s")

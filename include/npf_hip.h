@@ -25,6 +25,8 @@
  *   npf_cast_bf16_weights  bf16 weight images for the bf16 compute mode (no reference counterpart)
  *   npf_prepare_weights    the two above, batched over the layers of a chain (no reference counterpart)
  *   npf_gather_points    CntxtTrgtGetter.select              npf/utils/datasplit.py:246-255
+ *   npf_masked_attn_fwd/bwd, npf_masked_mean_fwd/bwd  DotAttender.forward / torch.mean(R_cntxt, dim=1) of a padded batch
+ *                        whose per-task context sizes are device data (no reference counterpart: the reference cuts the batch)
  *   npf_split_heads/npf_merge_heads  MultiheadAttender._make_multiheaded / _concatenate_multiheads
  *                                                         npf/architectures/attention.py:505-527
  *
@@ -455,6 +457,36 @@ int npf_b16_run(const npf_x6_op_t *ops, int32_t n_ops, const float *out_w, const
                 int32_t tiles_per_task, int32_t per_task, int32_t width, int32_t variant, void *stream);
 /* npf_x6_task_images with the rounded value alone: row_img / tr_img [n_tasks][F][F] bf16. */
 int npf_b16_task_images(const float *src, int32_t n_tasks, int32_t pts, int32_t width, void *row_img, void *tr_img, void *stream);
+
+/* ---- padded contexts: per-task counts as device data (csrc/masked_kernels.hip) -------------------------------------------
+ * The batch holds n_keys (attention) / pts_per_task (mean) context rows per task, of which the first n_valid[task] are real:
+ * n_valid is a DEVICE int32 [n_tasks] tensor the kernels read (values outside [0, n_keys] are clamped there), the host never
+ * does -- the launch can sit in a captured graph and see new counts at every replay.  What the rows beyond the count hold
+ * (NaN included) has no influence on any result.
+ *
+ * Scaled-dot attention of n_queries queries over the first n_valid[task] keys of every task (DotAttender.forward on the batch cut
+ * per task, npf/architectures/attention.py:129-164,204-220):
+ *   out(b, q, :) = sum_{k < n_valid[b]} softmax_{k < n_valid[b]}(scale <Q(b,q,:), K(b,k,:)>) V(b,k,:),   0 if n_valid[b] == 0.
+ * q / out: PT32 [n_tasks][n_queries][d], k / v: PT32 [n_tasks][n_keys][d] (tiles of roundup(d, 32) features), d % 4 == 0, d <= 256, any
+ * n_keys: the keys are walked in blocks with an online softmax, blocks wholly beyond the count are skipped.  Multihead attention:
+ * the heads as extra tasks (npf_split_heads: task h * n_tasks + b) with n_valid repeated per head.  lse [n_tasks][n_queries] (or NULL at
+ * inference): log-sum-exp of the scaled scores over the real keys (0 where there is none), what the backward pass recomputes the
+ * probabilities from.  fp32 MFMA.  Every element of out (whole tiles) is written.
+ * npf_masked_attn_bwd: d_q / d_k / d_v (PT32, shapes of q / k / v, every element written); rows k >= n_valid[b] of d_k / d_v are exact
+ * zeros, and so is d_q where n_valid[b] == 0.
+ * Status: NPF_EINVAL (nothing launched) for d % 4 != 0, d > 256 or a negative count of tasks / keys / queries. */
+int npf_masked_attn_fwd(const float *q, const float *k, const float *v, const int32_t *n_valid, int32_t n_tasks, int32_t n_keys,
+                        int32_t n_queries, int32_t d, float scale, float *out, float *lse, void *stream);
+int npf_masked_attn_bwd(const float *q, const float *k, const float *v, const int32_t *n_valid, const float *out, const float *d_out,
+                        const float *lse, int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d, float scale, float *d_q,
+                        float *d_k, float *d_v, void *stream);
+/* out[task][F] (row-major) = mean over the first n_valid[task] points of PT32 tensor R (F % 32 == 0), zeros if n_valid[task] == 0
+ * (torch.mean(R_cntxt, dim=1) on the batch cut per task, np.py:95, attnnp.py:181); tiles beyond the count are not read. */
+int npf_masked_mean_fwd(const float *R_pt, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *out,
+                        void *stream);
+/* dR_pt[task][p][f] (+)= d_out[task][f] / n_valid[task] for p < n_valid[task], 0 beyond (accumulate as npf_mean_agg_bwd). */
+int npf_masked_mean_bwd(const float *d_out, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *dR_pt,
+                        int32_t accumulate, void *stream);
 
 int npf_version(void);
 

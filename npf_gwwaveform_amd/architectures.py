@@ -390,6 +390,13 @@ def merge_flat_input(module, is_sum_merge=False, **kwargs):
     return merged_flat_input
 
 
+def _no_bf16_masked():
+    from . import chain as _chain
+
+    if _chain.COMPUTE_DTYPE != "fp32":
+        raise NotImplementedError("per-task context counts (n_valid / n_cntxt) are not implemented in the bf16 compute mode")
+
+
 class DotAttender(nn.Module):
     """Scaled dot-product cross attention without learned projections:
     ``softmax(Q K^T / sqrt(d)) V`` (npf/architectures/attention.py:89-220)."""
@@ -417,11 +424,17 @@ class DotAttender(nn.Module):
         """Can ``append_to`` keep a whole score row in registers (else: ``attend_pt``)."""
         return n_keys <= NPF_MAX_FUSED_ROW
 
-    def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None):
+    def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None, n_valid=None):
         """PT32 in, PT32 out, any number of keys (fused chain up to 256 keys, blocked softmax of
-        attention_long.py beyond)."""
+        attention_long.py beyond).  ``n_valid``: device integer tensor [n_tasks], the number of real keys of every task among
+        the ``n_keys`` rows (a padded batch): the masked attention kernel (``functional.masked_attention``)."""
         from .attention_long import long_scaledot_attention
 
+        if n_valid is not None:
+            _no_bf16_masked()
+            scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
+            return FN.masked_attention(queries_pt, keys_pt, values_pt, n_valid, queries_pt.shape[0], n_keys, n_queries,
+                                       self.kq_size, scale)
         if self.fits_fused(n_keys):
             ch = Chain(queries_pt.shape[0], n_queries, queries_pt.device, wg_per_task=True)
             ch.input_pt(queries_pt, self.kq_size)
@@ -432,13 +445,18 @@ class DotAttender(nn.Module):
         return long_scaledot_attention(queries_pt, keys_pt, values_pt, n_keys, n_queries, self.value_size, scale,
                                        k_tr=keys_tr, v_tr=values_tr, d=self.kq_size)
 
-    def forward(self, keys, queries, values):
+    def forward(self, keys, queries, values, n_valid=None):
+        if n_valid is not None and keys.dim() != 3:
+            raise NotImplementedError("n_valid with 4-D (relative-position) keys is not implemented")
         B, C, d = keys.shape
         T = queries.shape[1]
         if keys.dim() != 3 or queries.dim() != 3:
             raise NotImplementedError("relative-position (4-D) keys are not on the hot path")
         if C == 0:
             raise ValueError("attention over zero keys")
+        if n_valid is not None:
+            o = self.attend_pt(FN.pack_pt(queries), FN.pack_pt(keys), FN.pack_pt(values), C, T, n_valid=n_valid)
+            return FN.unpack_pt(o, T, self.out_size)
         if not self.fits_fused(C):
             o = self.attend_pt(FN.pack_pt(queries), FN.pack_pt(keys), FN.pack_pt(values), C, T)
             return FN.unpack_pt(o, T, self.out_size)
@@ -491,10 +509,19 @@ class MultiheadAttender(nn.Module):
         ch.input_pt(x_pt, lin.in_features).linear(lin.weight, lin.bias).output_pt()
         return ch.run()[0]
 
-    def _heads_attention(self, queries_pt, keys_pt, values_pt, B, C, T, queries_proj=None):
+    def _heads_attention(self, queries_pt, keys_pt, values_pt, B, C, T, queries_proj=None, n_valid=None):
         """K/Q/V projections, per-head scaled-dot attention, heads merged: PT32 [B, T, value_size].  ``queries_proj``: the query
-        projection when the launch that encoded the queries already made it (x6.xenc_proj)."""
+        projection when the launch that encoded the queries already made it (x6.xenc_proj).  ``n_valid``: real keys per task of a
+        padded batch -- the heads-as-tasks route with the counts repeated per head (task h * B + b)."""
         H, d = self.n_heads, self.kq_size
+        if n_valid is not None:
+            _no_bf16_masked()
+            Kh = FN.split_heads(self._project(keys_pt, B, C, self.key_transform), B, C, d, H)
+            Qp = queries_proj if queries_proj is not None else self._project(queries_pt, B, T, self.query_transform)
+            Qh = FN.split_heads(Qp, B, T, d, H)
+            Vh = FN.split_heads(self._project(values_pt, B, C, self.value_transform), B, C, self.value_size, H)
+            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=FN.counts_i32(n_valid, B).repeat(H))
+            return FN.merge_heads(Oh, B, T, self.value_size, H)
         if FN.mha_usable(self.kq_head_size, self.value_head_size, C):
             # 16- / 32-feature heads (the reference's default r_dim = 128 with 8 heads; 256 with 8): one launch on the projected
             # tensors, the heads are feature slices of the PT32 tiles (csrc/mha_kernel.hip)
@@ -519,20 +546,20 @@ class MultiheadAttender(nn.Module):
         return FN.merge_heads(Oh, B, T, self.value_size, H)
 
     def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None,
-                  queries_proj=None):
+                  queries_proj=None, n_valid=None):
         B = queries_pt.shape[0]
-        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, n_queries, queries_proj)
+        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, n_queries, queries_proj, n_valid=n_valid)
         if self.post_processor is not None:
             ctx = self._project(ctx, B, n_queries, self.post_processor)
         return ctx
 
-    def forward(self, keys, queries, values, rel_pos_enc=None, **kwargs):
+    def forward(self, keys, queries, values, rel_pos_enc=None, n_valid=None, **kwargs):
         if rel_pos_enc is not None or keys.dim() != 3:
             raise NotImplementedError("relative position encodings are not on the hot path")
         C, T = keys.shape[1], queries.shape[1]
         if C == 0:
             raise ValueError("attention over zero keys")
-        o = self.attend_pt(FN.pack_pt(queries), FN.pack_pt(keys), FN.pack_pt(values), C, T)
+        o = self.attend_pt(FN.pack_pt(queries), FN.pack_pt(keys), FN.pack_pt(values), C, T, n_valid=n_valid)
         return FN.unpack_pt(o, T, self.out_size)
 
 
@@ -550,9 +577,9 @@ class TransformerAttender(MultiheadAttender):
         self.reset_parameters()
 
     def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None,
-                  queries_proj=None):
+                  queries_proj=None, n_valid=None):
         B, T, d = queries_pt.shape[0], n_queries, self.out_size
-        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, T, queries_proj)
+        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, T, queries_proj, n_valid=n_valid)
         ln1, ln2 = self.layer_norm1, self.layer_norm2
         if FN.add_layernorm_usable(d):
             x = FN.add_layernorm(ctx, queries_pt, ln1, B, T)  # (a bandwidth-bound kernel of its own: csrc/ln_kernel.hip)

@@ -352,4 +352,4 @@ extern "C" int npf_mean_agg_bwd(const float* d_out, int32_t n_tasks, int32_t pts
   return NPF_OK;
 }
 
-extern "C" int npf_version(void) { return 1; }
+extern "C" int npf_version(void) { return 2; }

@@ -1,0 +1,439 @@
+// Attention and mean over PADDED contexts whose real sizes are data on the device (npf_masked_attn_fwd / _bwd, npf_masked_mean_fwd /
+// _bwd): every task b has n_valid[b] real context points out of the n_keys rows its tensors hold, and n_valid is an int32 tensor the
+// kernels read -- the host never does, so a launch can sit in a captured graph and see new counts at every replay.
+//
+// What they compute, in the reference's terms: DotAttender.forward (npf/architectures/attention.py:129-164, 204-220) and
+// torch.mean(R_cntxt, dim=1) (npf/neuralproc/np.py:95, attnnp.py:181) of the batch whose task b was cut to its first n_valid[b]
+// context points.
+//
+// Attention: scaled-dot, one head, feature widths d = 4 ... 256 (heads of a multihead attention come as extra tasks, npf_split_heads).
+// fp32 throughout on v_mfma_f32_16x16x4_f32 with the operand roles of mha_kernel.hip (the first contraction TRANSPOSED, so the
+// probabilities are directly the B operand of the second).  Keys are walked in blocks of KB = 32 (16 at the 256-wide instance) through
+// LDS with an online softmax: running maximum m and sum l per query, the accumulator rescaled by exp(m_old - m_new) -- no limit on
+// n_keys.  The walk ends at n_valid[b]: blocks wholly beyond it are never staged or multiplied, and inside the last block the rows
+// beyond it are staged as zeros and their scores set to -inf, so whatever the padding rows hold (NaN included) never meets a
+// multiply.  The backward pass recomputes the probabilities from the saved log-sum-exp in two kernels: d_q like the forward pass
+// (a workgroup = 64 queries, walking the key blocks), d_k / d_v with a workgroup per 16 keys whose four waves walk the queries and
+// meet in LDS -- no atomics, so the result does not depend on the launch.  Rows >= n_valid[b] of d_k / d_v are stored as zeros.
+#include "npf_common.hpp"
+
+namespace npf {
+
+// feature f of point p of a task's PT32 tensor with Fp (padded) features
+__device__ __forceinline__ size_t mk_pt(int task, int tiles, int Fp, int p, int f) {
+  return ((((size_t)task * tiles + (p >> 5)) * (Fp >> 2) + (f >> 2)) * 32 + (p & 31)) * 4 + (f & 3);
+}
+
+__device__ __forceinline__ f32x4 mk_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+__device__ __forceinline__ float mk_sum4(float v) {  // over the four lanes (g = 0..3) that share a column
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+__device__ __forceinline__ float mk_max4(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16));
+  v = fmaxf(v, __shfl_xor(v, 32));
+  return v;
+}
+
+// the task's count, clamped to what its tensors hold
+__device__ __forceinline__ int mk_count(const int32_t* __restrict__ n_valid, int b, int n_keys) {
+  const int n = n_valid[b];
+  return n < 0 ? 0 : (n > n_keys ? n_keys : n);
+}
+
+// rows key0 .. key0 + KB - 1 of a task's PT32 tensor into LDS, LD floats apart (LD even); rows >= nv and features >= d as zeros
+template <int DP, int KB, int LD>
+__device__ __forceinline__ void mk_stage(const float* __restrict__ X, int b, int tiles, int Fp, int d, int key0, int nv, float* S,
+                                         int tid) {
+  for (int i = tid; i < KB * (DP / 4); i += 256) {
+    const int p = i % KB, f4 = i / KB, key = key0 + p;
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    if (key < nv && 4 * f4 < d) x = *(const f32x4*)(X + mk_pt(b, tiles, Fp, key, 4 * f4));
+    *(float2*)(S + p * LD + 4 * f4) = float2{x[0], x[1]};
+    *(float2*)(S + p * LD + 4 * f4 + 2) = float2{x[2], x[3]};
+  }
+}
+
+template <int DP>
+struct MkGeom {
+  static constexpr int KB = DP == 256 ? 16 : 32;  // keys per block: 33 KB of LDS for keys + values at every width
+  static constexpr int NSB = KB / 16, NKC = DP / 4, NDT = DP / 16;
+  // row strides: an A operand read [row = lane % 16][k = lane / 16] is conflict-free at LD = 2 mod 32, a read
+  // [row = 4 (lane / 16) + j][lane % 16] at LD = 4 mod 32 (ds_read_b32: 32 banks, the two halves of the wave apart)
+  static constexpr int LDA = DP + 2, LDB = DP + 4;
+};
+
+// One workgroup = one task and 64 queries (16 per wave); DP = the tile width the instance computes on (d <= DP).
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                             const float* __restrict__ V, const int32_t* __restrict__ n_valid,
+                                                             float* __restrict__ O, float* __restrict__ lse, int n_keys, int T,
+                                                             int Fp, int d, float scale) {
+  using G = MkGeom<DP>;
+  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
+  __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
+  __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int qblocks = (T + 63) >> 6;
+  const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int nv = mk_count(n_valid, b, n_keys);
+  const int q = qb * 64 + wave * 16 + c;
+  const bool live = q < T;
+  float Qq[NKC];  // the lane's query as an operand: Q[q][4 kc + g]
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc) Qq[kc] = (live && 4 * kc < d) ? Q[mk_pt(b, tilesT, Fp, q, 4 * kc) + g] : 0.f;
+  f32x4 o[NDT];  // O^T[dv = 16 dt + 4 g + i][q = c], not yet divided by l
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  for (int key0 = 0; key0 < nv; key0 += KB) {  // (nv is uniform over the workgroup)
+    __syncthreads();
+    mk_stage<DP, KB, LDK>(K, b, tilesC, Fp, d, key0, nv, Ks, tid);
+    mk_stage<DP, KB, LDV>(V, b, tilesC, Fp, d, key0, nv, Vs, tid);
+    __syncthreads();
+    f32x4 S[NSB];  // S^T[key = key0 + 16 sb + 4 g + i][q = c]
+    float bm = -INFINITY;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) acc = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], acc);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        acc[i] = (key0 + 16 * sb + 4 * g + i < nv) ? acc[i] * scale : -INFINITY;
+        bm = fmaxf(bm, acc[i]);
+      }
+      S[sb] = acc;
+    }
+    // (key0 < nv: the block has a real key, so its maximum is finite)
+    const float m_new = fmaxf(m, mk_max4(bm));
+    const float alpha = expf(m - m_new);  // (0 at the first block: m = -inf)
+    float ps = 0.f;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        S[sb][i] = expf(S[sb][i] - m_new);  // (exp(-inf) = 0 beyond the count)
+        ps += S[sb][i];
+      }
+    l = l * alpha + mk_sum4(ps);
+    m = m_new;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) o[dt] = mk_mfma(Vs[(16 * sb + 4 * g + j) * LDV + 16 * dt + c], S[sb][j], o[dt]);
+  }
+  const float inv = (live && l > 0.f) ? 1.f / l : 0.f;  // (no real key: zeros; the tile's rows beyond T: zeros)
+  if (q < tilesT * 32) {
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+      if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = o[dt] * inv;
+  }
+  if (live && g == 0 && lse != nullptr) lse[(size_t)b * T + q] = nv > 0 ? m + logf(l) : 0.f;
+}
+
+// d_q: the forward pass's geometry.  dS^T = scale P^T (dP^T - D), P from the log-sum-exp, D[q] = <dO[q], O[q]>.
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                            const float* __restrict__ V, const int32_t* __restrict__ n_valid,
+                                                            const float* __restrict__ O, const float* __restrict__ dO,
+                                                            const float* __restrict__ lse, float* __restrict__ dQ, int n_keys, int T,
+                                                            int Fp, int d, float scale) {
+  using G = MkGeom<DP>;
+  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDA;
+  __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
+  __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int qblocks = (T + 63) >> 6;
+  const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int nv = mk_count(n_valid, b, n_keys);
+  const int q = qb * 64 + wave * 16 + c;
+  const bool live = q < T;
+  float Qq[NKC], Gq[NKC];
+  // D as the diagonal of O dO^T on the matrix unit, i.e. summed in the order dP^T = V dO^T is: where one key takes all the weight
+  // (O = that key's V) the difference dP - D then cancels exactly instead of to the rounding of two differently ordered sums
+  f32x4 dd = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc) {
+    const bool ok = live && 4 * kc < d;
+    const size_t at = mk_pt(b, tilesT, Fp, ok ? q : 0, ok ? 4 * kc : 0) + g;
+    Qq[kc] = ok ? Q[at] : 0.f;
+    Gq[kc] = ok ? dO[at] : 0.f;
+    dd = mk_mfma(ok ? O[at] : 0.f, Gq[kc], dd);  // [row = query 4 g + i][column = query c]
+  }
+  // (row c of column c sits in the lane of group c / 4, element c % 4)
+  const int e = c & 3;
+  const float Dc = __shfl(e == 0 ? dd[0] : e == 1 ? dd[1] : e == 2 ? dd[2] : dd[3], c + 16 * (c >> 2));
+  const float Lc = live ? lse[(size_t)b * T + q] : 0.f;
+  f32x4 dq[NDT];  // dQ^T[f = 16 dt + 4 g + i][q = c]
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int key0 = 0; key0 < nv; key0 += KB) {
+    __syncthreads();
+    mk_stage<DP, KB, LDK>(K, b, tilesC, Fp, d, key0, nv, Ks, tid);
+    mk_stage<DP, KB, LDV>(V, b, tilesC, Fp, d, key0, nv, Vs, tid);
+    __syncthreads();
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) {
+      f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) {
+        st = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], st);
+        dpt = mk_mfma(Vs[(16 * sb + c) * LDV + 4 * kc + g], Gq[kc], dpt);
+      }
+      f32x4 dst;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float p = (live && key0 + 16 * sb + 4 * g + i < nv) ? expf(st[i] * scale - Lc) : 0.f;
+        dst[i] = scale * p * (dpt[i] - Dc);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) dq[dt] = mk_mfma(Ks[(16 * sb + 4 * g + j) * LDK + 16 * dt + c], dst[j], dq[dt]);
+    }
+  }
+  if (q < tilesT * 32) {  // (zeros where the task has no real key, and in the tile's rows beyond T)
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+      if (16 * dt + 4 * g < Fp) *(f32x4*)(dQ + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = dq[dt];
+  }
+}
+
+// d_k / d_v: one workgroup = one task and 16 keys; its four waves take the 16-query blocks in turn, keep dK^T / dV^T of the 16 keys in
+// registers and add them up through LDS.  Blocks beyond the count only store their zeros.
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                             const float* __restrict__ V, const int32_t* __restrict__ n_valid,
+                                                             const float* __restrict__ O, const float* __restrict__ dO,
+                                                             const float* __restrict__ lse, float* __restrict__ dK,
+                                                             float* __restrict__ dV, int n_keys, int T, int Fp, int d, float scale) {
+  using G = MkGeom<DP>;
+  constexpr int NKC = G::NKC, NDT = G::NDT, LD = G::LDA;
+  __shared__ __attribute__((aligned(16))) float Ks[16 * LD];
+  __shared__ __attribute__((aligned(16))) float Vs[16 * LD];
+  __shared__ f32x4 red[3 * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int kblocks = 2 * tilesC;  // (whole tiles: every row of d_k / d_v is written)
+  const int kb = blockIdx.x % kblocks, b = blockIdx.x / kblocks;
+  const int nv = mk_count(n_valid, b, n_keys);
+  const int key0 = 16 * kb;
+  if (key0 >= nv) {  // (uniform over the workgroup)
+    for (int i = tid; i < 16 * (Fp >> 2); i += 256) {
+      const size_t at = mk_pt(b, tilesC, Fp, key0 + (i & 15), 4 * (i >> 4));
+      *(f32x4*)(dK + at) = f32x4{0.f, 0.f, 0.f, 0.f};
+      *(f32x4*)(dV + at) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    return;
+  }
+  mk_stage<DP, 16, LD>(K, b, tilesC, Fp, d, key0, nv, Ks, tid);
+  mk_stage<DP, 16, LD>(V, b, tilesC, Fp, d, key0, nv, Vs, tid);
+  __syncthreads();
+  f32x4 aK[NDT], aV[NDT];  // dK^T / dV^T [f = 16 dt + 4 g + i][key = key0 + c]
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) aK[dt] = aV[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool key_ok = key0 + c < nv;
+  for (int q0 = wave * 16; q0 < T; q0 += 64) {
+    const int q = q0 + c;
+    const bool live = q < T;
+    // S[q = q0 + 4 g + i][key = c] and dP alike; D and the log-sum-exp of the lane's query c on the way
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dd = {0.f, 0.f, 0.f, 0.f};  // dO O^T [row = query 4 g + i][column = query c]: D on its diagonal, summed as dP is
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) {
+      const bool ok = live && 4 * kc < d;
+      const size_t at = mk_pt(b, tilesT, Fp, ok ? q : 0, ok ? 4 * kc : 0) + g;
+      const float qv = ok ? Q[at] : 0.f, gv = ok ? dO[at] : 0.f;
+      dd = mk_mfma(gv, ok ? O[at] : 0.f, dd);
+      s = mk_mfma(qv, Ks[c * LD + 4 * kc + g], s);
+      dp = mk_mfma(gv, Vs[c * LD + 4 * kc + g], dp);
+    }
+    const float Lc = live ? lse[(size_t)b * T + q] : 0.f;
+    f32x4 pr, ds;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      // (row 4 g + i of column 4 g + i: element i of the lane of this group whose column is 4 g + i; lane 4 g + i holds query
+      // q0 + 4 g + i as its column)
+      const float Di = __shfl(dd[i], 20 * g + i), Li = __shfl(Lc, 4 * g + i);
+      pr[i] = (key_ok && q0 + 4 * g + i < T) ? expf(s[i] * scale - Li) : 0.f;
+      ds[i] = scale * pr[i] * (dp[i] - Di);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int qj = q0 + 4 * g + j;
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) {
+        const int f = 16 * dt + c;
+        const bool ok = qj < T && f < d;
+        const size_t at = mk_pt(b, tilesT, Fp, ok ? qj : 0, ok ? (f & ~3) : 0) + (f & 3);
+        aV[dt] = mk_mfma(ok ? dO[at] : 0.f, pr[j], aV[dt]);  // A[row = f][k = query 4 g + j]
+        aK[dt] = mk_mfma(ok ? Q[at] : 0.f, ds[j], aK[dt]);
+      }
+    }
+  }
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      const f32x4 mine = pass == 0 ? aK[dt] : aV[dt];
+      __syncthreads();
+      if (wave > 0) red[(wave - 1) * 64 + lane] = mine;
+      __syncthreads();
+      if (wave == 0 && 16 * dt + 4 * g < Fp) {
+        f32x4 t = mine;
+#pragma unroll
+        for (int w = 0; w < 3; ++w) t += red[w * 64 + lane];
+        if (!key_ok) t = f32x4{0.f, 0.f, 0.f, 0.f};
+        *(f32x4*)((pass == 0 ? dK : dV) + mk_pt(b, tilesC, Fp, key0 + c, 16 * dt + 4 * g)) = t;
+      }
+    }
+  }
+}
+
+// out[task][f] = mean over the first n_valid[task] points.  grid = (F / 32, n_tasks); 256 threads = 8 feature quads x 32 points;
+// tiles beyond the count are not read.
+__global__ void masked_mean_fwd_kernel(const float* __restrict__ R, const int32_t* __restrict__ n_valid, int pts, int F,
+                                       float* __restrict__ out) {
+  const int tiles = (pts + 31) / 32;
+  const int p = threadIdx.x & 31, f4 = blockIdx.x * 8 + (threadIdx.x >> 5);
+  const size_t task = blockIdx.y;
+  const int nv = mk_count(n_valid, (int)task, pts);
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  const float* base = R + task * tiles * (size_t)(F * 32) + pt_off(f4, p);
+  for (int t = 0; t * 32 < nv; ++t)
+    if (t * 32 + p < nv) s += *(const f32x4*)(base + (size_t)t * F * 32);
+#pragma unroll
+  for (int off = 16; off >= 1; off >>= 1)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] += __shfl_xor(s[j], off);
+  if (p == 0) *(f32x4*)(out + task * F + 4 * f4) = nv > 0 ? s * (1.f / (float)nv) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+__global__ void masked_mean_bwd_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ n_valid, int n_tasks, int pts,
+                                       int F, float* __restrict__ dR, int accumulate) {
+  const int tiles = (pts + 31) / 32;
+  const size_t total = (size_t)n_tasks * tiles * (F / 4) * 32;
+  for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int p = idx & 31;
+    const size_t r = idx >> 5;
+    const int f4 = r % (F / 4);
+    const size_t tt = r / (F / 4);
+    const int tile = tt % tiles;
+    const size_t task = tt / tiles;
+    const int nv = mk_count(n_valid, (int)task, pts);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (tile * 32 + p < nv) v = *(const f32x4*)(d_out + task * F + 4 * f4) * (1.f / (float)nv);
+    if (accumulate) v += *(const f32x4*)(dR + idx * 4);
+    *(f32x4*)(dR + idx * 4) = v;
+  }
+}
+
+}  // namespace npf
+
+static bool mk_misaligned(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) != 0;
+}
+
+static int masked_attn_check(const void* q, const void* k, const void* v, const void* n_valid, int32_t n_tasks, int32_t n_keys,
+                             int32_t n_queries, int32_t d) {
+  if (n_tasks < 0 || n_keys < 0 || n_queries < 0 || d <= 0 || (d & 3) || d > 256) return NPF_EINVAL;
+  if (!q || !n_valid || (n_keys > 0 && (!k || !v)) || mk_misaligned(q, k, v)) return NPF_EINVAL;
+  return NPF_OK;
+}
+
+#define MK_DISPATCH(LAUNCH) \
+  do {                      \
+    if (d <= 32) {          \
+      LAUNCH(32);           \
+    } else if (d <= 64) {   \
+      LAUNCH(64);           \
+    } else if (d <= 128) {  \
+      LAUNCH(128);          \
+    } else {                \
+      LAUNCH(256);          \
+    }                       \
+  } while (0)
+
+extern "C" int npf_masked_attn_fwd(const float* q, const float* k, const float* v, const int32_t* n_valid, int32_t n_tasks,
+                                   int32_t n_keys, int32_t n_queries, int32_t d, float scale, float* out, float* lse, void* stream) {
+  const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
+  if (rc != NPF_OK) return rc;
+  if (!out || mk_misaligned(out)) return NPF_EINVAL;
+  if (n_tasks == 0 || n_queries == 0) return NPF_OK;
+  const int Fp = npf::round_up(d, 32);
+  const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define MK_FWD(DP) \
+  hipLaunchKernelGGL(npf::masked_attn_fwd_kernel<DP>, grid, block, 0, st, q, k, v, n_valid, out, lse, n_keys, n_queries, Fp, d, scale)
+  MK_DISPATCH(MK_FWD);
+#undef MK_FWD
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_attn_bwd(const float* q, const float* k, const float* v, const int32_t* n_valid, const float* out,
+                                   const float* d_out, const float* lse, int32_t n_tasks, int32_t n_keys, int32_t n_queries,
+                                   int32_t d, float scale, float* d_q, float* d_k, float* d_v, void* stream) {
+  const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
+  if (rc != NPF_OK) return rc;
+  if (!out || !d_out || !lse || !d_q || (n_keys > 0 && (!d_k || !d_v))) return NPF_EINVAL;
+  if (mk_misaligned(out, d_out, d_q) || mk_misaligned(d_k, d_v)) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  const int Fp = npf::round_up(d, 32);
+  const dim3 block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (n_queries > 0) {
+    const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64));
+#define MK_DQ(DP)                                                                                                                  \
+  hipLaunchKernelGGL(npf::masked_attn_dq_kernel<DP>, grid, block, 0, st, q, k, v, n_valid, out, d_out, lse, d_q, n_keys, n_queries, \
+                     Fp, d, scale)
+    MK_DISPATCH(MK_DQ);
+#undef MK_DQ
+    NPF_CHECK_LAUNCH();
+  }
+  if (n_keys > 0) {  // (no queries: the walk over them is empty and the kernel stores the zeros)
+    const dim3 grid((unsigned)n_tasks * (2 * ((n_keys + 31) / 32)));
+#define MK_DKV(DP)                                                                                                                \
+  hipLaunchKernelGGL(npf::masked_attn_dkv_kernel<DP>, grid, block, 0, st, q, k, v, n_valid, out, d_out, lse, d_k, d_v, n_keys, \
+                     n_queries, Fp, d, scale)
+    MK_DISPATCH(MK_DKV);
+#undef MK_DKV
+    NPF_CHECK_LAUNCH();
+  }
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_mean_fwd(const float* R_pt, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* out,
+                                   void* stream) {
+  if (!R_pt || !n_valid || !out || n_tasks < 0 || pts <= 0 || F <= 0 || (F & 31) || mk_misaligned(R_pt, out)) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  hipLaunchKernelGGL(npf::masked_mean_fwd_kernel, dim3(F / 32, n_tasks), dim3(256), 0, (hipStream_t)stream, R_pt, n_valid, pts, F,
+                     out);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_mean_bwd(const float* d_out, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* dR_pt,
+                                   int32_t accumulate, void* stream) {
+  if (!d_out || !n_valid || !dR_pt || n_tasks < 0 || pts <= 0 || F <= 0 || (F & 31) || mk_misaligned(d_out, dR_pt)) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  const size_t total = (size_t)n_tasks * ((pts + 31) / 32) * (F / 4) * 32;
+  size_t g = (total + 255) / 256;
+  if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(npf::masked_mean_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, d_out, n_valid, n_tasks, pts,
+                     F, dR_pt, accumulate);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}

@@ -52,10 +52,22 @@ class GetRangeIndcs:
 
 
 class GetRandomIndcs:
-    """Random subset of indices (datasplit.py:60-145), drawn on ``device``."""
+    """Random subset of indices (datasplit.py:60-145), drawn on ``device``.
+
+    ``is_per_task=True`` (no reference counterpart; the reference draws one size per batch): one count PER TASK between the
+    same ``a`` and ``b``, drawn on the device with the same ``torch.Generator`` as the indices (no host sync, Python's
+    ``random`` is not touched).  The indices come back padded to the largest possible count ``_point_count(b, n)`` -- a
+    shape that does not change from batch to batch, which is what a captured graph needs -- and the counts of the last
+    draw are in ``last_counts`` (int64 [batch_size]): row ``i`` uses its first ``last_counts[i]`` indices, the model takes
+    the counts as ``n_cntxt``.  The default keeps the reference's behaviour."""
 
     def __init__(self, a=0.1, b=0.5, is_batch_share=False, range_indcs=None, is_ensure_one=False,
-                 is_beta_binomial=False, proba_uniform=0):
+                 is_beta_binomial=False, proba_uniform=0, is_per_task=False):
+        if is_per_task and (is_beta_binomial or proba_uniform):
+            raise NotImplementedError("is_per_task draws uniform counts on the device; is_beta_binomial / proba_uniform "
+                                      "are host-side draws of one size per batch")
+        self.is_per_task = is_per_task
+        self.last_counts = None
         self.a, self.b = a, b
         self.is_batch_share = is_batch_share
         self.range_indcs = range_indcs
@@ -79,7 +91,13 @@ class GetRandomIndcs:
     def __call__(self, batch_size, n_possible_points, device=None, generator: Optional[torch.Generator] = None):
         if self.range_indcs is not None:
             n_possible_points = self.range_indcs[1] - self.range_indcs[0]
-        n = self.n_indcs(n_possible_points)
+        if self.is_per_task:
+            lo, n = _point_count(self.a, n_possible_points), _point_count(self.b, n_possible_points)
+            if self.is_ensure_one:
+                lo, n = max(lo, 1), max(n, 1)
+            self.last_counts = torch.randint(lo, n + 1, (batch_size,), device=device, generator=generator)
+        else:
+            n = self.n_indcs(n_possible_points)
         if self.is_batch_share:
             indcs = torch.randperm(n_possible_points, device=device, generator=generator)[:n]
             indcs = indcs.unsqueeze(0).expand(batch_size, n)
@@ -94,7 +112,10 @@ class GetRandomIndcs:
 
 class CntxtTrgtGetter:
     """Split (X, y) into context and target points (datasplit.py:148-255): ``getter(X, y)`` ->
-    ``X_cntxt, Y_cntxt, X_trgt, Y_trgt``.  Same constructor arguments, call signature and overridable hooks
+    ``X_cntxt, Y_cntxt, X_trgt, Y_trgt`` -- and, behind a ``contexts_getter`` with ``is_per_task=True``, a fifth value
+    ``n_cntxt`` (int64 [B], on the device): the context comes padded to a fixed number of rows, task ``b`` owns the first
+    ``n_cntxt[b]`` and the rows beyond are zero-filled; :meth:`batch` returns the same as the dict a model / ``Trainer.step`` takes.
+    Same constructor arguments, call signature and overridable hooks
     (``preprocess_context``, ``add_cntxts_to_trgts``, ``getter_inputs``, ``select``) as the reference; the work is
     two steps: :meth:`indices` decides which points go where (device-side draws unless the caller supplies them),
     :meth:`select` moves them (one gather launch per side)."""
@@ -128,7 +149,19 @@ class CntxtTrgtGetter:
         if is_return_indcs:
             return ctx, X_for_context, trg, X
         # caller-supplied indices are range-checked (one host sync); the getters' own draws are in range by construction
-        return (*self.select(X_for_context, y, ctx, validate=supplied), *self.select(X, y, trg, validate=supplied))
+        Xc, Yc = self.select(X_for_context, y, ctx, validate=supplied)
+        Xt, Yt = self.select(X, y, trg, validate=supplied)
+        if context_indcs is None and getattr(self.contexts_getter, "is_per_task", False):
+            n_cntxt = self.contexts_getter.last_counts
+            pad = (torch.arange(Xc.shape[1], device=Xc.device).unsqueeze(0) >= n_cntxt.unsqueeze(1)).unsqueeze(-1)
+            return Xc.masked_fill(pad, 0.0), Yc.masked_fill(pad, 0.0), Xt, Yt, n_cntxt
+        return Xc, Yc, Xt, Yt
+
+    def batch(self, X, y=None, **kwargs) -> dict:
+        """The split as the dict ``Trainer.step`` / ``eval_loglike`` take: ``X_cntxt, Y_cntxt, X_trgt, Y_trgt`` and, with a
+        per-task contexts getter, ``n_cntxt``."""
+        out = self(X, y, **kwargs)
+        return dict(zip(("X_cntxt", "Y_cntxt", "X_trgt", "Y_trgt", "n_cntxt"), out))
 
     # ---- hooks of the reference ---------------------------------------------------------------------------------
     def preprocess_context(self, X):

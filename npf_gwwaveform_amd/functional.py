@@ -350,3 +350,111 @@ def add_layernorm(a_pt: torch.Tensor, b_pt: torch.Tensor, ln: torch.nn.LayerNorm
     """PT32 LayerNorm(a + b) with the module's gamma / beta / eps (``add_layernorm_usable``)."""
     F = ln.normalized_shape[0]
     return _AddLayerNormFn.apply(a_pt, b_pt, ln.weight, ln.bias, ln.eps, n_tasks, pts, F)
+
+
+# ---- padded contexts: per-task counts as device data (csrc/masked_kernels.hip) -------------------------------------------
+MASKED_MAX_WIDTH = 256  # feature width of npf_masked_attn_fwd / _bwd
+
+
+def counts_i32(n_valid: torch.Tensor, n_tasks: int, what: str = "n_valid") -> torch.Tensor:
+    """The per-task counts as the contiguous device int32 [n_tasks] tensor the masked kernels read.  An int64 tensor is converted on
+    the device; the values are never read by the host (the kernels clamp them to the rows the tensors hold)."""
+    if not isinstance(n_valid, torch.Tensor):
+        raise ValueError(f"{what} must be an integer device tensor of shape [{n_tasks}], got {type(n_valid).__name__}")
+    if n_valid.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what} must be int32 or int64, got {n_valid.dtype}")
+    if tuple(n_valid.shape) != (n_tasks,):
+        raise ValueError(f"{what} must have shape [{n_tasks}] (one count per task), got {list(n_valid.shape)}")
+    if not n_valid.is_cuda:
+        raise ValueError(f"{what} must live on the device (its values are read by the kernels, never by the host)")
+    return n_valid.to(torch.int32).contiguous()
+
+
+def _iptr(t: torch.Tensor) -> int:
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    return t.data_ptr()
+
+
+class _MaskedAttnFn(torch.autograd.Function):
+    """out[b, q] = softmax over the first n_valid[b] keys of scale <Q[b, q], K[b, k]> times V on PT32 tensors (``npf_masked_attn_fwd`` /
+    ``_bwd``; DotAttender.forward, npf/architectures/attention.py:129-164,204-220, of the batch cut per task)."""
+
+    @staticmethod
+    def forward(ctx, q_pt, k_pt, v_pt, n_valid, n_tasks, n_keys, n_queries, d, scale):
+        from . import chain as CH
+
+        q_pt, k_pt, v_pt = q_pt.contiguous(), k_pt.contiguous(), v_pt.contiguous()
+        train = any(ctx.needs_input_grad[:3])
+        out = torch.empty(CH.pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
+        lse = torch.empty((n_tasks, n_queries), dtype=torch.float32, device=q_pt.device) if train else None
+        if CH.PROFILE is not None:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        L.check(L.load().npf_masked_attn_fwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), n_tasks, n_keys, n_queries, d,
+                                             float(scale), L.ptr(out), L.ptr(lse) if lse is not None else None, L.stream_ptr()),
+                "npf_masked_attn_fwd")
+        if CH.PROFILE is not None:
+            ev1.record()
+            CH.PROFILE.append(("masked_attn_fwd_kernel", 4 * n_tasks * n_queries * n_keys * d, ev0, ev1,
+                               4 * pad32(d) * n_tasks * (2 * n_queries + 2 * n_keys), "masked attention (flops at full counts)"))
+        ctx.geom = (n_tasks, n_keys, n_queries, d, float(scale))
+        if train:
+            ctx.save_for_backward(q_pt, k_pt, v_pt, n_valid, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import chain as CH
+
+        n_tasks, n_keys, n_queries, d, scale = ctx.geom
+        q_pt, k_pt, v_pt, n_valid, out, lse = ctx.saved_tensors
+        g = g.contiguous()
+        dq, dk, dv = torch.empty_like(q_pt), torch.empty_like(k_pt), torch.empty_like(v_pt)  # (written whole)
+        if CH.PROFILE is not None:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        L.check(L.load().npf_masked_attn_bwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), L.ptr(out), L.ptr(g), L.ptr(lse),
+                                             n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.stream_ptr()),
+                "npf_masked_attn_bwd")
+        if CH.PROFILE is not None:
+            ev1.record()
+            CH.PROFILE.append(("masked_attn_bwd_kernels", 16 * n_tasks * n_queries * n_keys * d, ev0, ev1,
+                               4 * pad32(d) * n_tasks * (6 * n_queries + 4 * n_keys), "masked attention backward (flops at full counts)"))
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def masked_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, n_keys: int,
+                     n_queries: int, d: int, scale: float) -> torch.Tensor:
+    """PT32 [n_tasks, n_queries, d]: scaled-dot attention of every task's queries over the first ``n_valid[task]`` of its ``n_keys``
+    keys / values (zeros where a task has none).  ``n_valid``: device int32 / int64 [n_tasks], read by the kernel only -- no host
+    sync, so the call can be captured in a graph and replayed with new counts.  ``d`` % 4 == 0, ``d`` <= 256, any ``n_keys``."""
+    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
+        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
+    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale)
+
+
+class _MaskedMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pt, n_valid, n_tasks, pts, F):
+        Fp = pad32(F)
+        ctx.geo = (n_tasks, pts, Fp)
+        ctx.save_for_backward(n_valid)
+        out = torch.empty((n_tasks, Fp), dtype=torch.float32, device=pt.device)
+        L.check(L.load().npf_masked_mean_fwd(L.ptr(pt.contiguous()), _iptr(n_valid), n_tasks, pts, Fp, L.ptr(out), L.stream_ptr()),
+                "npf_masked_mean_fwd")
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        n_tasks, pts, Fp = ctx.geo
+        (n_valid,) = ctx.saved_tensors
+        d = pt_empty(n_tasks, pts, Fp, g.device)
+        L.check(L.load().npf_masked_mean_bwd(L.ptr(g.contiguous()), _iptr(n_valid), n_tasks, pts, Fp, L.ptr(d), 0, L.stream_ptr()),
+                "npf_masked_mean_bwd")
+        return d, None, None, None, None
+
+
+def masked_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
+    """Mean over the first ``n_valid[task]`` points of a PT32 tensor -> row-major [n_tasks, pad32(F)] (zeros where a task has none):
+    ``torch.mean(R, dim=1)`` (npf/neuralproc/np.py:95, attnnp.py:181) of the batch cut per task; counts as in :func:`masked_attention`."""
+    return _MaskedMeanFn.apply(R_pt, counts_i32(n_valid, n_tasks), n_tasks, pts, F)

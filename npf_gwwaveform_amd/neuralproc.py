@@ -127,13 +127,25 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         return d
 
     # ------------------------------------------------------------------ forward
-    def forward(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt=None):
-        """Same contract as base.py:177-239: returns ``(p_yCc, z_samples, q_zCc, q_zCct)``."""
+    def forward(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt=None, n_cntxt=None):
+        """Same contract as base.py:177-239: returns ``(p_yCc, z_samples, q_zCc, q_zCct)``.
+
+        ``n_cntxt``: per-task context sizes of a PADDED batch -- an integer device tensor [B] (int32 or int64), task ``b`` uses
+        the rows ``X_cntxt[b, :n_cntxt[b]]`` / ``Y_cntxt[b, :n_cntxt[b]]`` and everything returned for it equals what the
+        single-task batch cut to those rows returns.  The counts are read by the kernels only (no host sync): a step captured
+        in a graph is replayed with new counts.  The rows beyond the count have no influence on any output or gradient, but the
+        training-time range check covers them too: padding must be finite and inside [-1, 1] (fill it with zeros).  ``X_cntxt``
+        with zero rows behaves as without ``n_cntxt``.  Not implemented with ``n_cntxt``: self-attention context encoders
+        (``is_self_attn=True``) and the bf16 compute mode."""
+        if n_cntxt is not None:
+            n_cntxt = self._check_n_cntxt(n_cntxt, X_cntxt)
         self._validate_inputs(X_cntxt, Y_cntxt, X_trgt, Y_trgt)
         B, C, _ = X_cntxt.shape
         T = X_trgt.shape[1]
         if T == 0:
             raise ValueError("no target points")
+        if n_cntxt is not None and C > 0:
+            return self._forward_padded(X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt)
         from . import chain as _chain
 
         fused_t = self._fused_target_side(C, T)
@@ -170,8 +182,46 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         p_yCc = self._head(suff, Y_trgt, B, T)
         return p_yCc, z_samples, q_zCc, q_zCct
 
+    def _check_n_cntxt(self, n_cntxt, X_cntxt):
+        """The per-task context sizes as a device int32 [B] tensor; refuses what the padded path does not implement."""
+        from . import chain as _chain
+
+        if getattr(self, "is_self_attn", False):
+            raise NotImplementedError("n_cntxt is not implemented for self-attention context encoders (is_self_attn=True)")
+        if _chain.COMPUTE_DTYPE != "fp32":
+            raise NotImplementedError("n_cntxt is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
+        n = FN.counts_i32(n_cntxt, X_cntxt.shape[0], "n_cntxt")
+        if n.device != X_cntxt.device:
+            raise ValueError(f"n_cntxt lives on {n.device}, the batch on {X_cntxt.device}")
+        return n
+
+    def _forward_padded(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt):
+        """``forward`` over a padded batch (``n_cntxt``: device int32 [B]).  The per-point stages -- x-encoder, XY-encoder, over all
+        rows of the padded context -- and the decoder keep the launches of an unfused step; what ties the points of a task together
+        (attention over the context, the mean over it) runs on the masked kernels (csrc/masked_kernels.hip).  The fused target
+        side (x6.target_side) is not taken: its softmax has the key count as a launch argument."""
+        B, C, _ = X_cntxt.shape
+        T = X_trgt.shape[1]
+        if self._fused_context_side(C):
+            from . import x6
+
+            Xc_pt, R_pts = x6.context_side(self, X_cntxt, Y_cntxt)
+            R = self._pool_pt(R_pts, B, n_valid=n_cntxt)
+        else:
+            Xc_pt = self._xenc_pt(X_cntxt)
+            R = self._encode_globally_pt(Xc_pt, Y_cntxt, B, C, n_valid=n_cntxt)
+        Xt_pt = self._xenc_pt(X_trgt)
+        if self.encoded_path in ["latent", "both"]:
+            z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T, n_valid=n_cntxt)
+        else:
+            z_samples, q_zCc, q_zCct = None, None, None
+        if self.encoded_path == "latent":
+            R = None
+        suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=n_cntxt)
+        return self._head(suff, Y_trgt, B, T), z_samples, q_zCc, q_zCct
+
     def _validate_inputs(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt):
-        """base.py:241-247: features must be in [-1, 1] during training."""
+        """base.py:241-247: features must be in [-1, 1] during training (the padding rows of a padded batch included)."""
         for t in (X_cntxt, Y_cntxt, X_trgt, Y_trgt):
             if t is not None and (not t.is_cuda or t.dtype != torch.float32):
                 raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
@@ -232,11 +282,12 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         ch.input_rows(X.contiguous(), dx)
         return self.x_encoder.append_to(ch).run_pt(as_weights=with_tr)
 
-    def _xyenc_pt(self, X_enc: PTensor, Y) -> PTensor:
+    def _xyenc_pt(self, X_enc: PTensor, Y, with_tr: Optional[bool] = None) -> PTensor:
         """Per-point XY encoding (the per-point part of encode_globally) -> [B, P, r]."""
         ch = Chain(X_enc.n_tasks, X_enc.pts, Y.device)
         ch.input_rows(Y.contiguous(), self.y_dim)
-        return self.xy_encoder.run_pt(ch, X_enc.t, X_enc.n_tasks, X_enc.pts, with_tr=self._attentive)
+        return self.xy_encoder.run_pt(ch, X_enc.t, X_enc.n_tasks, X_enc.pts,
+                                      with_tr=self._attentive if with_tr is None else with_tr)
 
     def _head(self, suff, Y_trgt, B, T):
         return HeadDistribution(suff, self.y_dim, not self.is_heteroskedastic, suff.shape[0] // B, B, T)
@@ -332,8 +383,9 @@ class LatentNeuralProcessFamily(NeuralProcessFamily):
             q_zCct, sampling_dist = None, q_zCc
         return sampling_dist.rsample([self.n_z_samples]), q_zCc, q_zCct
 
-    def _latent_path_pt(self, R, C, Xt_pt, Y_trgt, B, T):
-        q_zCc = self._latent_dist_from(self._lat_input(R, B))
+    def _latent_path_pt(self, R, C, Xt_pt, Y_trgt, B, T, n_valid=None):
+        # (n_valid: the context sizes of a padded batch; the target-side encode below is over the targets and is not masked)
+        q_zCc = self._latent_dist_from(self._lat_input(R, B) if n_valid is None else self._lat_input(R, B, n_valid=n_valid))
         if self.is_q_zCct and Y_trgt is not None:
             if Xt_pt is None:
                 # (forward left the target side to one x6 program, which encodes the targets itself: the target-side latent
@@ -407,17 +459,20 @@ class CNP(NeuralProcessFamily):
         return R.expand(B, T, self.r_dim).unsqueeze(0)
 
     # fused path
-    def _encode_globally_pt(self, X_enc, Y, B, P):
+    def _encode_globally_pt(self, X_enc, Y, B, P, n_valid=None):
         """-> row-major R [B, 1, r] (np.py:86-101)."""
         if P == 0:
             return torch.zeros(B, 1, self.r_dim, device=Y.device)
-        return self._pool_pt(self._xyenc_pt(X_enc, Y), B)
+        return self._pool_pt(self._xyenc_pt(X_enc, Y), B, n_valid=n_valid)
 
-    def _pool_pt(self, R_pts: PTensor, B):
-        """np.py:95: the mean over the context points of the per-point representations -> row-major [B, 1, r]."""
+    def _pool_pt(self, R_pts: PTensor, B, n_valid=None):
+        """np.py:95: the mean over the context points of the per-point representations -> row-major [B, 1, r]; ``n_valid``: over
+        the first ``n_valid[b]`` of them (a padded batch; zeros for a task without context, as ``encode_globally`` at C = 0)."""
+        if n_valid is not None:
+            return FN.masked_mean(R_pts.t, n_valid, B, R_pts.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
         return FN.mean_agg(R_pts.t, R_pts.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
         return self._decode_taskvec(Xt_pt, R.reshape(B, self.r_dim), B, T, B)
 
 
@@ -429,7 +484,7 @@ class LNP(LatentNeuralProcessFamily, CNP):
     def __init__(self, x_dim, y_dim, encoded_path="latent", **kwargs):
         super().__init__(x_dim, y_dim, encoded_path=encoded_path, **kwargs)
 
-    def _lat_input(self, R, B):
+    def _lat_input(self, R, B, n_valid=None):
         return R
 
     def _rep_rows(self, z_samples, R, B):
@@ -447,7 +502,7 @@ class LNP(LatentNeuralProcessFamily, CNP):
         n_z = z_samples.size(0)
         return self._rep_rows(z_samples, R, B).reshape(n_z, B, 1, self.r_dim).expand(n_z, B, T, self.r_dim)
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
         n_z = z_samples.size(0)
         return self._decode_taskvec(Xt_pt, self._rep_rows(z_samples, R, B), B, T, n_z * B)
 
@@ -506,15 +561,25 @@ class AttnCNP(NeuralProcessFamily):
         return R_trgt.unsqueeze(0)
 
     # fused path
-    def _encode_globally_pt(self, X_enc, Y, B, P):
+    def _encode_globally_pt(self, X_enc, Y, B, P, n_valid=None):
         """-> R_cntxt [B, P, r] as a PTensor (attnnp.py:105-116); None when there is no context."""
         if P == 0:
             return None
-        return self._xyenc_pt(X_enc, Y)
+        # (a padded batch attends on the masked kernel, which reads the PT32 tensors: no feature-major copies)
+        return self._xyenc_pt(X_enc, Y, with_tr=None if n_valid is None else False)
 
-    def _pool_pt(self, R_pts: PTensor, B):
+    def _pool_pt(self, R_pts: PTensor, B, n_valid=None):
         """attnnp.py:105-116: no pooling, one representation per context point."""
         return R_pts
+
+    def _attend_padded(self, Xc_pt, R, Xt_pt, B, C, T, n_valid):
+        """PT32 [B, T, r]: attention of the targets over the first ``n_valid[b]`` context points of every task (attnnp.py:118-131
+        on the batch cut per task).  A task without context gets zeros, as ``trgt_dependent_representation`` at C = 0 -- also
+        behind an attender whose learned layers would turn zero context vectors into something else."""
+        R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid)
+        if not isinstance(self.attender, DotAttender):
+            R_t = R_t * (n_valid > 0).to(R_t.dtype).view(B, 1, 1, 1, 1)
+        return R_t
 
     def _attend_into(self, ch, Xc_pt, R, Xt_pt, C, T, tap_x1: bool = False):
         """cur of ``ch`` <- attention of the targets over the context (attnnp.py:118-131): fused into
@@ -543,7 +608,16 @@ class AttnCNP(NeuralProcessFamily):
             ch.input_pt(self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, keys_tr=Xc_pt.tr, values_tr=R.tr), self.r_dim)
         return ch
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
+        if n_valid is not None:  # (a padded batch: masked attention, then the decoder as an unfused step runs it)
+            from . import x6
+
+            R_t = self._attend_padded(Xc_pt, R, Xt_pt, B, C, T, n_valid)
+            if x6.decoder_side_usable(self, T):
+                return x6.decoder_side(self, R_t, Xt_pt.t, T)
+            ch = Chain(B, T, Xt_pt.t.device, wg_per_task=True)
+            ch.input_pt(R_t, self.r_dim)
+            return self.decoder.finish_rows(ch, x1_pt=Xt_pt.t)
         if Xt_pt is None:  # (forward left the target side to the fused x6 program: x-encoder, attention, decoder in one launch)
             from . import x6
 
@@ -583,10 +657,13 @@ class AttnLNP(LatentNeuralProcessFamily, AttnCNP):
             return torch.zeros(B, 1, self.r_dim, device=R.device)
         return FN.mean_agg(FN.pack_pt(R), C, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
 
-    def _lat_input(self, R: Optional[PTensor], B):
-        """attnnp.py:172-181: the latent path pools the per-point representation (its own point count)."""
+    def _lat_input(self, R: Optional[PTensor], B, n_valid=None):
+        """attnnp.py:172-181: the latent path pools the per-point representation (its own point count; ``n_valid``: the first
+        ``n_valid[b]`` points of a padded batch)."""
         if R is None:
             return torch.zeros(B, 1, self.r_dim, device=self.r_z_merger.weight.device)
+        if n_valid is not None:
+            return FN.masked_mean(R.t, n_valid, B, R.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
         return FN.mean_agg(R.t, R.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
 
     def trgt_dependent_representation(self, X_cntxt, z_samples, R, X_trgt):
@@ -604,7 +681,7 @@ class AttnLNP(LatentNeuralProcessFamily, AttnCNP):
         return (type(self) is AttnLNP and self.n_z_samples == 1 and self.z_dim == self.r_dim
                 and x6.target_side_usable(self, C, T, latent_merge=True))
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
         n_z = z_samples.size(0)
         dev = z_samples.device
         W, b, r = self.r_z_merger.weight, self.r_z_merger.bias, self.r_dim
@@ -617,22 +694,27 @@ class AttnLNP(LatentNeuralProcessFamily, AttnCNP):
             from . import x6
 
             return x6.target_side(self, self._X_trgt_raw, Xc_pt, R, zb=zb)
-        if n_z == 1 and C > 0 and not isinstance(self.attender, DotAttender) and self.z_dim == self.r_dim:
+        R_pad = self._attend_padded(Xc_pt, R, Xt_pt, B, C, T, n_valid) if n_valid is not None else None
+        if n_z == 1 and C > 0 and (R_pad is not None or not isinstance(self.attender, DotAttender)) and self.z_dim == self.r_dim:
             from . import x6
 
             if x6.decoder_side_usable(self, T):  # (attention with learned projections, then merge_r_z + decoder as one program)
-                R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, queries_proj=Xt_pt.proj)
+                R_t = R_pad if R_pad is not None else self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, queries_proj=Xt_pt.proj)
                 return x6.decoder_side(self, R_t, Xt_pt.t, T, zb=zb[:, :r].contiguous())
         if n_z == 1:
             ch = Chain(B, T, dev, wg_per_task=True)
             if C == 0:
                 ch.input_pt(torch.zeros(pt_shape(B, T, r), device=dev), r)
+            elif R_pad is not None:
+                ch.input_pt(R_pad, r)
             else:
                 self._attend_into(ch, Xc_pt, R, Xt_pt, C, T)
             mod = 0
         else:
             if C == 0:
                 R_det = torch.zeros(pt_shape(B, T, r), device=dev)
+            elif R_pad is not None:
+                R_det = R_pad
             else:
                 cha = Chain(B, T, dev, wg_per_task=True)
                 self._attend_into(cha, Xc_pt, R, Xt_pt, C, T).output_pt()

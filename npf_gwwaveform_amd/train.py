@@ -48,6 +48,11 @@ def get_exponential_decay_gamma(scheduling_factor, max_epochs):
     return (1 / scheduling_factor) ** (1 / max_epochs)
 
 
+def _n_cntxt_of(batch: dict) -> dict:
+    """The per-task context sizes of a padded batch as the model's keyword argument (nothing for a batch without them)."""
+    return {"n_cntxt": batch["n_cntxt"]} if batch.get("n_cntxt") is not None else {}
+
+
 class Trainer:
     """forward -> loss -> backward -> (bucketed all-reduce) -> Adam, on flat parameter /
     gradient buffers."""
@@ -61,7 +66,9 @@ class Trainer:
         collective inside a captured region; the exchange is latency-bound -- 3-5 MB -- and is then not hidden behind the
         backward pass, which costs less than the host time of an eager step at these sizes; ``use_graph=False`` keeps the
         bucketed all-reduce overlapped with the backward pass).  Needs fixed batch shapes (a new shape or learning rate
-        re-captures).  The range check of the inputs (base.py:241-247) stays in the step as a device reduction; its verdict
+        re-captures; ``n_captures`` counts them).  Batches whose context size changes keep ONE graph when they come padded to a
+        fixed number of rows with the per-task sizes as ``batch["n_cntxt"]`` (``GetRandomIndcs(is_per_task=True)``): the sizes
+        are a static input like the other batch tensors, only their shape is part of the graph's signature.  The range check of the inputs (base.py:241-247) stays in the step as a device reduction; its verdict
         is read at the next sync point: call :meth:`check_inputs` (e.g. once per epoch) to get the reference's ValueError."""
         self.model, self.criterion = model, criterion
         # ``defer_input_check``: eagerly launched steps, too, keep the range check of base.py:241-247 on the device and leave its
@@ -82,6 +89,7 @@ class Trainer:
         self._graph = None
         self._graph_opt = None
         self._eager_steps = 0
+        self.n_captures = 0  # how often a step was captured (a new batch shape or learning rate captures again)
         # set to a list to time the phases of every eager step with HIP events on the launch stream (bench.py): entries are
         # (start of backward, end of backward, gradient exchange finished); ``phase_times()`` reads them after a sync
         self.phase_events = None
@@ -172,6 +180,7 @@ class Trainer:
                 self.model.validate_inputs = was
             if self._graph is None:
                 return self._eager_step(batch)
+            self.n_captures += 1
             self._graph_sig = sig  # (a capture records, it does not execute: this batch runs in the replay below)
         for k, v in batch.items():
             self._static[k].copy_(v)
@@ -195,7 +204,7 @@ class Trainer:
         for p in self.flat.params:
             p.grad = None
         self.reducer.reset()
-        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"])
+        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"], **_n_cntxt_of(batch))
         loss = self.criterion(out, batch["Y_trgt"])
         loss.backward()
         self.flat.flat.grad = self.reducer.finish()
@@ -205,7 +214,7 @@ class Trainer:
         for p in self.flat.params:
             p.grad = None
         self.reducer.reset()
-        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"])
+        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"], **_n_cntxt_of(batch))
         loss = self.criterion(out, batch["Y_trgt"])
         timed = self.phase_events is not None and loss.is_cuda
         if timed:
