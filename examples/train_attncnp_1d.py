@@ -3,7 +3,7 @@
 random context / target split on the device, AttnCNP with transformer attention (what the
 reference's notebooks and shipped checkpoints use), Adam, checkpoint in skorch's layout.
 
-    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16]
+    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged]
 
 Only the import line differs from a script written against the reference:
     from npf import AttnCNP, CNPFLoss                      # reference
@@ -43,9 +43,15 @@ def main():
     ap.add_argument("--per-task-contexts", action="store_true",
                     help="every task draws its own context size; the batch comes padded with the sizes as n_cntxt and the "
                          "step is replayed from ONE captured graph (implies --graph)")
+    ap.add_argument("--ragged", action="store_true",
+                    help="waveforms of different lengths: every task has its own number of samples (between a quarter of --points "
+                         "and --points), the data set comes padded with the lengths as n_points, the batch carries n_cntxt and "
+                         "n_trgt, and ONE captured graph serves every mix (implies --per-task-contexts)")
     ap.add_argument("--out", default="/tmp/npf_example_ckpt")
     args = ap.parse_args()
     dev = "cuda:0"
+    if args.ragged:
+        args.per_task_contexts = True
     if args.per_task_contexts:
         args.graph = True
     A.set_compute_dtype(args.dtype)
@@ -64,7 +70,12 @@ def main():
     t0 = time.perf_counter()
     for step in range(args.steps):
         X, Y = functions(args.tasks, args.points, dev, seed=step)
-        loss = trainer.step(split.batch(X, Y))
+        if args.ragged:  # (lengths drawn on the device; the samples beyond a task's length are padding the getter never picks)
+            n = torch.randint(args.points // 4, args.points + 1, (args.tasks,), device=dev,
+                              generator=torch.Generator(device=dev).manual_seed(10 ** 6 + step))
+            loss = trainer.step(split.batch(X, Y, n_points=n))
+        else:
+            loss = trainer.step(split.batch(X, Y))
         if (step + 1) % 50 == 0:
             print(f"step {step + 1:5d}  loss/task {loss.item():9.3f}  lr {trainer.end_epoch():.2e}  "
                   f"{(step + 1) * args.tasks * args.points / (time.perf_counter() - t0):,.0f} target-points/s")

@@ -17,6 +17,7 @@
  *                        pool_and_replicate_middle        npf/neuralproc/helpers.py:21-32,
  *                        sum_log_prob                     npf/losses.py:18-24
  *   npf_gauss_head_bwd   autograd of the above
+ *   npf_masked_gauss_head_fwd/bwd  the same over a batch of padded targets whose per-task sizes are device data
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -25,7 +26,7 @@
  *   npf_cast_bf16_weights  bf16 weight images for the bf16 compute mode (no reference counterpart)
  *   npf_prepare_weights    the two above, batched over the layers of a chain (no reference counterpart)
  *   npf_gather_points    CntxtTrgtGetter.select              npf/utils/datasplit.py:246-255
- *   npf_masked_attn_fwd/bwd, npf_masked_mean_fwd/bwd  DotAttender.forward / torch.mean(R_cntxt, dim=1) of a padded batch
+ *   npf_masked_attn_fwd/bwd (and _fwd_nq / _bwd_nq: padded queries too), npf_masked_mean_fwd/bwd  DotAttender.forward / torch.mean(R_cntxt, dim=1) of a padded batch
  *                        whose per-task context sizes are device data (no reference counterpart: the reference cuts the batch)
  *   npf_split_heads/npf_merge_heads  MultiheadAttender._make_multiheaded / _concatenate_multiheads
  *                                                         npf/architectures/attention.py:505-527
@@ -223,6 +224,20 @@ int npf_gauss_head_bwd(const float *suff, const float *loc, const float *scale, 
                        int32_t dy, int32_t homoskedastic, const float *Y, int32_t n_y_rows,
                        const float *d_loc, const float *d_scale, const float *d_sum_logp, float *d_suff,
                        void *stream);
+
+/* Padded targets: row r owns the first n_valid[r % n_tasks] of its pts target rows.  n_valid is a DEVICE int32 [n_tasks] tensor the
+ * kernels read (clamped to [0, pts]); n_rows % n_tasks == 0 and, with Y, n_y_rows % n_tasks == 0.  loc / scale / sum_logp and the
+ * homoskedastic pooling (divided by the count) cover the rows below the count only and equal npf_gauss_head_fwd of the row cut to
+ * them (bit for bit at full counts); rows beyond: loc = 0, scale = 1.  sum_logp of a row without targets is 0.  suff and Y beyond the
+ * count are never read.  Otherwise the arguments of npf_gauss_head_fwd. */
+int npf_masked_gauss_head_fwd(const float *suff, const int32_t *n_valid, int32_t n_tasks, int32_t n_rows, int32_t pts, int32_t dy,
+                              int32_t homoskedastic, const float *Y, int32_t n_y_rows, float *loc, float *scale,
+                              float *sum_logp, void *stream);
+/* d_suff of the above: every row is written, the rows at and beyond the count as zeros (so nothing upstream -- decoder, attention,
+ * x-encoder -- gets a gradient from padding); d_loc / d_scale beyond the count are not read. */
+int npf_masked_gauss_head_bwd(const float *suff, const float *loc, const float *scale, const int32_t *n_valid, int32_t n_tasks,
+                              int32_t n_rows, int32_t pts, int32_t dy, int32_t homoskedastic, const float *Y, int32_t n_y_rows,
+                              const float *d_loc, const float *d_scale, const float *d_sum_logp, float *d_suff, void *stream);
 
 /* ---- Monte-Carlo objectives over the latent samples (npf/losses.py:126-276) ------------ */
 /* log_w: row-major [n_z][n_tasks], the log weight of latent sample k for task b: sum_t log p(y_t | z_k), plus
@@ -480,6 +495,17 @@ int npf_masked_attn_fwd(const float *q, const float *k, const float *v, const in
 int npf_masked_attn_bwd(const float *q, const float *k, const float *v, const int32_t *n_valid, const float *out, const float *d_out,
                         const float *lse, int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d, float scale, float *d_q,
                         float *d_k, float *d_v, void *stream);
+/* The same with a count of real QUERIES per task as well (padded targets): n_q_valid is a DEVICE int32 [n_tasks] tensor, clamped to
+ * [0, n_queries]; with heads as extra tasks the caller repeats it per head like n_valid.  Rows q >= n_q_valid[b] of out / d_q are
+ * exact zeros (lse = 0) and q / out / d_out / lse beyond the count are never read; workgroups wholly beyond it return before they
+ * stage a key, and the walk of the d_k / d_v kernel over the queries ends at the count.  The rows below the counts are bit-identical
+ * to npf_masked_attn_fwd / _bwd on the same tensors (with d_out zeroed beyond the query count): same block and summation order. */
+int npf_masked_attn_fwd_nq(const float *q, const float *k, const float *v, const int32_t *n_valid, const int32_t *n_q_valid,
+                           int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d, float scale, float *out, float *lse,
+                           void *stream);
+int npf_masked_attn_bwd_nq(const float *q, const float *k, const float *v, const int32_t *n_valid, const int32_t *n_q_valid,
+                           const float *out, const float *d_out, const float *lse, int32_t n_tasks, int32_t n_keys, int32_t n_queries,
+                           int32_t d, float scale, float *d_q, float *d_k, float *d_v, void *stream);
 /* out[task][F] (row-major) = mean over the first n_valid[task] points of PT32 tensor R (F % 32 == 0), zeros if n_valid[task] == 0
  * (torch.mean(R_cntxt, dim=1) on the batch cut per task, np.py:95, attnnp.py:181); tiles beyond the count are not read. */
 int npf_masked_mean_fwd(const float *R_pt, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *out,

@@ -424,17 +424,21 @@ class DotAttender(nn.Module):
         """Can ``append_to`` keep a whole score row in registers (else: ``attend_pt``)."""
         return n_keys <= NPF_MAX_FUSED_ROW
 
-    def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None, n_valid=None):
+    def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None, n_valid=None,
+                  n_q_valid=None):
         """PT32 in, PT32 out, any number of keys (fused chain up to 256 keys, blocked softmax of
         attention_long.py beyond).  ``n_valid``: device integer tensor [n_tasks], the number of real keys of every task among
-        the ``n_keys`` rows (a padded batch): the masked attention kernel (``functional.masked_attention``)."""
+        the ``n_keys`` rows (a padded batch): the masked attention kernel (``functional.masked_attention``).  ``n_q_valid`` (with
+        ``n_valid`` only): the number of real queries of every task; the rows beyond come back as zeros and are skipped."""
         from .attention_long import long_scaledot_attention
 
+        if n_q_valid is not None and n_valid is None:
+            raise NotImplementedError("n_q_valid needs n_valid: query counts are an option of the masked attention kernel")
         if n_valid is not None:
             _no_bf16_masked()
             scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
             return FN.masked_attention(queries_pt, keys_pt, values_pt, n_valid, queries_pt.shape[0], n_keys, n_queries,
-                                       self.kq_size, scale)
+                                       self.kq_size, scale, n_q_valid=n_q_valid)
         if self.fits_fused(n_keys):
             ch = Chain(queries_pt.shape[0], n_queries, queries_pt.device, wg_per_task=True)
             ch.input_pt(queries_pt, self.kq_size)
@@ -509,18 +513,22 @@ class MultiheadAttender(nn.Module):
         ch.input_pt(x_pt, lin.in_features).linear(lin.weight, lin.bias).output_pt()
         return ch.run()[0]
 
-    def _heads_attention(self, queries_pt, keys_pt, values_pt, B, C, T, queries_proj=None, n_valid=None):
+    def _heads_attention(self, queries_pt, keys_pt, values_pt, B, C, T, queries_proj=None, n_valid=None, n_q_valid=None):
         """K/Q/V projections, per-head scaled-dot attention, heads merged: PT32 [B, T, value_size].  ``queries_proj``: the query
         projection when the launch that encoded the queries already made it (x6.xenc_proj).  ``n_valid``: real keys per task of a
-        padded batch -- the heads-as-tasks route with the counts repeated per head (task h * B + b)."""
+        padded batch -- the heads-as-tasks route with the counts repeated per head (task h * B + b); ``n_q_valid``: real queries per
+        task, repeated likewise."""
         H, d = self.n_heads, self.kq_size
+        if n_q_valid is not None and n_valid is None:
+            raise NotImplementedError("n_q_valid needs n_valid: query counts are an option of the masked attention kernel")
         if n_valid is not None:
             _no_bf16_masked()
             Kh = FN.split_heads(self._project(keys_pt, B, C, self.key_transform), B, C, d, H)
             Qp = queries_proj if queries_proj is not None else self._project(queries_pt, B, T, self.query_transform)
             Qh = FN.split_heads(Qp, B, T, d, H)
             Vh = FN.split_heads(self._project(values_pt, B, C, self.value_transform), B, C, self.value_size, H)
-            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=FN.counts_i32(n_valid, B).repeat(H))
+            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=FN.counts_i32(n_valid, B).repeat(H),
+                                    n_q_valid=None if n_q_valid is None else FN.counts_i32(n_q_valid, B, "n_q_valid").repeat(H))
             return FN.merge_heads(Oh, B, T, self.value_size, H)
         if FN.mha_usable(self.kq_head_size, self.value_head_size, C):
             # 16- / 32-feature heads (the reference's default r_dim = 128 with 8 heads; 256 with 8): one launch on the projected
@@ -546,9 +554,10 @@ class MultiheadAttender(nn.Module):
         return FN.merge_heads(Oh, B, T, self.value_size, H)
 
     def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None,
-                  queries_proj=None, n_valid=None):
+                  queries_proj=None, n_valid=None, n_q_valid=None):
         B = queries_pt.shape[0]
-        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, n_queries, queries_proj, n_valid=n_valid)
+        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, n_queries, queries_proj, n_valid=n_valid,
+                                    n_q_valid=n_q_valid)
         if self.post_processor is not None:
             ctx = self._project(ctx, B, n_queries, self.post_processor)
         return ctx
@@ -577,9 +586,9 @@ class TransformerAttender(MultiheadAttender):
         self.reset_parameters()
 
     def attend_pt(self, queries_pt, keys_pt, values_pt, n_keys: int, n_queries: int, keys_tr=None, values_tr=None,
-                  queries_proj=None, n_valid=None):
+                  queries_proj=None, n_valid=None, n_q_valid=None):
         B, T, d = queries_pt.shape[0], n_queries, self.out_size
-        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, T, queries_proj, n_valid=n_valid)
+        ctx = self._heads_attention(queries_pt, keys_pt, values_pt, B, n_keys, T, queries_proj, n_valid=n_valid, n_q_valid=n_q_valid)
         ln1, ln2 = self.layer_norm1, self.layer_norm2
         if FN.add_layernorm_usable(d):
             x = FN.add_layernorm(ctx, queries_pt, ln1, B, T)  # (a bandwidth-bound kernel of its own: csrc/ln_kernel.hip)

@@ -129,6 +129,135 @@ __global__ __launch_bounds__(256) void gauss_head_bwd_kernel(const float* __rest
   }
 }
 
+// ---- padded targets: the head of a batch whose task b owns the first n_valid[b] of its pts target rows -------------------------
+// (npf_masked_gauss_head_fwd / _bwd).  n_valid is a DEVICE int32 [n_tasks] tensor (row r reads n_valid[r % n_tasks], clamped to
+// [0, pts]), so the launch can sit in a captured graph and see new counts at every replay.  Every loop over the points is bounded by
+// the count: a task with few targets costs few iterations and suff / Y beyond the count are never read (NaN there is harmless).
+// Forward: loc / scale / sum_logp / the homoskedastic pooling (divided by the count) over the rows below the count, in the order
+// of gauss_head_fwd_kernel -- full counts give its results bit for bit; rows beyond: loc = 0, scale = 1 (a valid Normal).
+// Backward: EVERY row of d_suff is written, the rows at and beyond the count as zeros.  That is what keeps the rest of the backward
+// pass correct without further masks: the decoder's dgrad of a zero row is zero, so the weight gradients, dO of the attention and
+// with it dK / dV, and the x-encoder's gradients get nothing from padding.
+__device__ __forceinline__ int head_count(const int32_t* __restrict__ n_valid, size_t row, int n_tasks, int pts) {
+  const int n = n_valid[row % (size_t)n_tasks];
+  return n < 0 ? 0 : (n > pts ? pts : n);
+}
+
+__global__ __launch_bounds__(256) void masked_gauss_head_fwd_kernel(const float* __restrict__ suff,
+                                                                    const int32_t* __restrict__ n_valid, int n_tasks, int pts, int dy,
+                                                                    int homosk, const float* __restrict__ Y, int n_y_rows,
+                                                                    float* __restrict__ loc, float* __restrict__ scale,
+                                                                    float* __restrict__ sum_logp) {
+  __shared__ float red[8];
+  __shared__ float pooled[32];
+  const size_t row = blockIdx.x;
+  const int nv = head_count(n_valid, row, n_tasks, pts);  // (uniform over the workgroup)
+  const float* s = suff + row * pts * (size_t)(2 * dy);
+  float* lo = loc + row * pts * (size_t)dy;
+  float* sc = scale + row * pts * (size_t)dy;
+  const float* y = Y ? Y + (row % n_y_rows) * pts * (size_t)dy : nullptr;
+  const int n = nv * dy;
+  if (homosk && nv > 0) {
+    for (int d = 0; d < dy; ++d) {
+      float part = 0.f;
+      for (int t = threadIdx.x; t < nv; t += blockDim.x) part += 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
+      const float tot = block_sum(part, red);
+      if (threadIdx.x == 0) pooled[d] = tot / (float)nv;
+    }
+    __syncthreads();
+  }
+  float lp = 0.f;
+  for (int e = threadIdx.x; e < n; e += blockDim.x) {
+    const int t = e / dy, d = e - t * dy;
+    const float mu = s[t * 2 * dy + d];
+    const float sg = homosk ? pooled[d] : 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
+    if (loc) {
+      lo[e] = mu;
+      sc[e] = sg;
+    }
+    if (y) {
+      const float diff = y[e] - mu;
+      lp += -(diff * diff) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
+    }
+  }
+  if (loc) {
+    for (int e = n + threadIdx.x; e < pts * dy; e += blockDim.x) {
+      lo[e] = 0.f;
+      sc[e] = 1.f;
+    }
+  }
+  if (sum_logp) {
+    const float tot = block_sum(lp, red);  // (0 for a task without targets)
+    if (threadIdx.x == 0) sum_logp[row] = tot;
+  }
+}
+
+__global__ __launch_bounds__(256) void masked_gauss_head_bwd_kernel(const float* __restrict__ suff, const float* __restrict__ loc,
+                                                                    const float* __restrict__ scale,
+                                                                    const int32_t* __restrict__ n_valid, int n_tasks, int pts, int dy,
+                                                                    int homosk, const float* __restrict__ Y, int n_y_rows,
+                                                                    const float* __restrict__ d_loc, const float* __restrict__ d_scale,
+                                                                    const float* __restrict__ d_sum_logp, float* __restrict__ d_suff) {
+  __shared__ float red[8];
+  __shared__ float pooled[32];
+  __shared__ float pooled_sg[32];
+  const size_t row = blockIdx.x;
+  const int nv = head_count(n_valid, row, n_tasks, pts);  // (uniform over the workgroup)
+  const size_t ebase = row * pts * (size_t)dy;
+  const float* s = suff + row * pts * (size_t)(2 * dy);
+  float* ds = d_suff + row * pts * (size_t)(2 * dy);
+  const float* y = Y ? Y + (row % n_y_rows) * pts * (size_t)dy : nullptr;
+  const float g = (d_sum_logp && y) ? d_sum_logp[row] : 0.f;
+  const int n = nv * dy;
+  for (int i = 2 * n + threadIdx.x; i < pts * 2 * dy; i += blockDim.x) ds[i] = 0.f;  // the rows at and beyond the count
+  if (nv == 0) return;  // (ahead of every barrier)
+  if (!scale && homosk) {
+    for (int d = 0; d < dy; ++d) {
+      float part = 0.f;
+      for (int t = threadIdx.x; t < nv; t += blockDim.x) part += 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
+      const float tot = block_sum(part, red);
+      if (threadIdx.x == 0) pooled_sg[d] = tot / (float)nv;
+    }
+    __syncthreads();
+  }
+  auto mu_of = [&](int e, int t, int d) { return loc ? loc[ebase + e] : s[t * 2 * dy + d]; };
+  auto sg_of = [&](int e, int t, int d) {
+    return scale ? scale[ebase + e] : (homosk ? pooled_sg[d] : 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]));
+  };
+  if (homosk) {
+    for (int d = 0; d < dy; ++d) {
+      float part = 0.f;
+      for (int t = threadIdx.x; t < nv; t += blockDim.x) {
+        const int e = t * dy + d;
+        const float sg = sg_of(e, t, d);
+        float dsg = d_scale ? d_scale[ebase + e] : 0.f;
+        if (y) {
+          const float diff = y[e] - mu_of(e, t, d);
+          dsg += g * (diff * diff / (sg * sg * sg) - 1.f / sg);
+        }
+        part += dsg;
+      }
+      const float tot = block_sum(part, red);
+      if (threadIdx.x == 0) pooled[d] = tot / (float)nv;
+    }
+    __syncthreads();
+  }
+  for (int e = threadIdx.x; e < n; e += blockDim.x) {
+    const int t = e / dy, d = e - t * dy;
+    const float mu = mu_of(e, t, d), sg = sg_of(e, t, d);
+    float dmu = d_loc ? d_loc[ebase + e] : 0.f;
+    float dsg = d_scale ? d_scale[ebase + e] : 0.f;
+    if (y) {
+      const float diff = y[e] - mu;
+      dmu += g * diff / (sg * sg);
+      dsg += g * (diff * diff / (sg * sg * sg) - 1.f / sg);
+    }
+    if (homosk) dsg = pooled[d];
+    ds[t * 2 * dy + d] = dmu;
+    ds[t * 2 * dy + dy + d] = dsg * 0.99f * softplus_grad(s[t * 2 * dy + dy + d]);
+  }
+}
+
 // ---- Monte-Carlo objectives over the latent samples ----------------------------------------------------------------
 // lw[k][b]: log weight of latent sample k for task b (sum_t log p(y_t | z_k) [+ log q(z_k|C) - log q(z_k|C,T)]).
 //   mode 0: mean_k lw                                    (first term of the ELBO,  npf/losses.py:126-150)
@@ -257,6 +386,35 @@ extern "C" int npf_gauss_head_bwd(const float* suff, const float* loc, const flo
   if (Y && n_y_rows <= 0) return NPF_EINVAL;
   hipLaunchKernelGGL(npf::gauss_head_bwd_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, loc, scale, pts, dy,
                      homoskedastic, Y, Y ? n_y_rows : 1, d_loc, d_scale, d_sum_logp, d_suff);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_gauss_head_fwd(const float* suff, const int32_t* n_valid, int32_t n_tasks, int32_t n_rows, int32_t pts,
+                                         int32_t dy, int32_t homoskedastic, const float* Y, int32_t n_y_rows, float* loc,
+                                         float* scale, float* sum_logp, void* stream) {
+  if (!suff || !n_valid || n_tasks <= 0 || n_rows <= 0 || n_rows % n_tasks != 0 || pts <= 0 || dy <= 0 || dy > 16) return NPF_EINVAL;
+  if ((loc == nullptr) != (scale == nullptr)) return NPF_EINVAL;
+  if (!loc && !sum_logp) return NPF_EINVAL;  // a launch that writes nothing
+  if (Y && (n_y_rows <= 0 || n_y_rows % n_tasks != 0)) return NPF_EINVAL;  // (rows that share a Y row share a count)
+  if (sum_logp && !Y) return NPF_EINVAL;
+  hipLaunchKernelGGL(npf::masked_gauss_head_fwd_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, n_valid, n_tasks, pts,
+                     dy, homoskedastic, Y, Y ? n_y_rows : 1, loc, scale, sum_logp);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_gauss_head_bwd(const float* suff, const float* loc, const float* scale, const int32_t* n_valid,
+                                         int32_t n_tasks, int32_t n_rows, int32_t pts, int32_t dy, int32_t homoskedastic,
+                                         const float* Y, int32_t n_y_rows, const float* d_loc, const float* d_scale,
+                                         const float* d_sum_logp, float* d_suff, void* stream) {
+  if (!suff || !d_suff || !n_valid || n_tasks <= 0 || n_rows <= 0 || n_rows % n_tasks != 0 || pts <= 0 || dy <= 0 || dy > 16)
+    return NPF_EINVAL;
+  if ((loc == nullptr) != (scale == nullptr)) return NPF_EINVAL;
+  if (!loc && (d_loc || d_scale)) return NPF_EINVAL;
+  if (Y && (n_y_rows <= 0 || n_y_rows % n_tasks != 0)) return NPF_EINVAL;
+  hipLaunchKernelGGL(npf::masked_gauss_head_bwd_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, loc, scale, n_valid,
+                     n_tasks, pts, dy, homoskedastic, Y, Y ? n_y_rows : 1, d_loc, d_scale, d_sum_logp, d_suff);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }

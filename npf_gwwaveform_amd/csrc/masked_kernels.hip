@@ -15,6 +15,12 @@
 // multiply.  The backward pass recomputes the probabilities from the saved log-sum-exp in two kernels: d_q like the forward pass
 // (a workgroup = 64 queries, walking the key blocks), d_k / d_v with a workgroup per 16 keys whose four waves walk the queries and
 // meet in LDS -- no atomics, so the result does not depend on the launch.  Rows >= n_valid[b] of d_k / d_v are stored as zeros.
+//
+// Query counts (npf_masked_attn_fwd_nq / _bwd_nq, the NQ instances of the same three kernels): task b has n_q_valid[b] real queries
+// out of n_queries (padded targets).  A workgroup whose 64 queries all lie beyond the count stores its zeros (O, d_q; lse = 0) and
+// returns before it stages a key block; inside the boundary block the queries beyond the count are not live; the d_k / d_v walk over
+// the queries ends at the count, so Q / O / dO / lse rows beyond it are never read.  Block order and summation order are those of
+// the instances without a query count: the rows below the counts come out bit-identical.
 #include "npf_common.hpp"
 
 namespace npf {
@@ -66,11 +72,12 @@ struct MkGeom {
 };
 
 // One workgroup = one task and 64 queries (16 per wave); DP = the tile width the instance computes on (d <= DP).
-template <int DP>
+// NQ: the task's queries beyond n_q_valid[b] are padding (zeros out, never read); without it n_q_valid is not looked at.
+template <int DP, bool NQ>
 __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                              const float* __restrict__ V, const int32_t* __restrict__ n_valid,
-                                                             float* __restrict__ O, float* __restrict__ lse, int n_keys, int T,
-                                                             int Fp, int d, float scale) {
+                                                             const int32_t* __restrict__ n_q_valid, float* __restrict__ O,
+                                                             float* __restrict__ lse, int n_keys, int T, int Fp, int d, float scale) {
   using G = MkGeom<DP>;
   constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
   __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
@@ -81,8 +88,18 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
   const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
   const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
   const int nv = mk_count(n_valid, b, n_keys);
+  const int nq = NQ ? mk_count(n_q_valid, b, T) : T;
   const int q = qb * 64 + wave * 16 + c;
-  const bool live = q < T;
+  if (NQ && qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zeros, no key staged
+    if (q < tilesT * 32) {
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+        if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (q < T && g == 0 && lse != nullptr) lse[(size_t)b * T + q] = 0.f;
+    return;
+  }
+  const bool live = q < nq;
   float Qq[NKC];  // the lane's query as an operand: Q[q][4 kc + g]
 #pragma unroll
   for (int kc = 0; kc < NKC; ++kc) Qq[kc] = (live && 4 * kc < d) ? Q[mk_pt(b, tilesT, Fp, q, 4 * kc) + g] : 0.f;
@@ -138,13 +155,14 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
       if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = o[dt] * inv;
   }
   if (live && g == 0 && lse != nullptr) lse[(size_t)b * T + q] = nv > 0 ? m + logf(l) : 0.f;
+  if (NQ && !live && q < T && g == 0 && lse != nullptr) lse[(size_t)b * T + q] = 0.f;
 }
 
 // d_q: the forward pass's geometry.  dS^T = scale P^T (dP^T - D), P from the log-sum-exp, D[q] = <dO[q], O[q]>.
-template <int DP>
+template <int DP, bool NQ>
 __global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                             const float* __restrict__ V, const int32_t* __restrict__ n_valid,
-                                                            const float* __restrict__ O, const float* __restrict__ dO,
+                                                            const int32_t* __restrict__ n_q_valid, const float* __restrict__ O, const float* __restrict__ dO,
                                                             const float* __restrict__ lse, float* __restrict__ dQ, int n_keys, int T,
                                                             int Fp, int d, float scale) {
   using G = MkGeom<DP>;
@@ -157,8 +175,17 @@ __global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __rest
   const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
   const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
   const int nv = mk_count(n_valid, b, n_keys);
+  const int nq = NQ ? mk_count(n_q_valid, b, T) : T;
   const int q = qb * 64 + wave * 16 + c;
-  const bool live = q < T;
+  if (NQ && qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zero d_q rows
+    if (q < tilesT * 32) {
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+        if (16 * dt + 4 * g < Fp) *(f32x4*)(dQ + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    return;
+  }
+  const bool live = q < nq;
   float Qq[NKC], Gq[NKC];
   // D as the diagonal of O dO^T on the matrix unit, i.e. summed in the order dP^T = V dO^T is: where one key takes all the weight
   // (O = that key's V) the difference dP - D then cancels exactly instead of to the rounding of two differently ordered sums
@@ -211,11 +238,12 @@ __global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __rest
 }
 
 // d_k / d_v: one workgroup = one task and 16 keys; its four waves take the 16-query blocks in turn, keep dK^T / dV^T of the 16 keys in
-// registers and add them up through LDS.  Blocks beyond the count only store their zeros.
-template <int DP>
+// registers and add them up through LDS.  Blocks beyond the count only store their zeros.  NQ: the walk over the queries ends at the
+// task's query count (the kernel's cost is linear in the queries walked).
+template <int DP, bool NQ>
 __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                              const float* __restrict__ V, const int32_t* __restrict__ n_valid,
-                                                             const float* __restrict__ O, const float* __restrict__ dO,
+                                                             const int32_t* __restrict__ n_q_valid, const float* __restrict__ O, const float* __restrict__ dO,
                                                              const float* __restrict__ lse, float* __restrict__ dK,
                                                              float* __restrict__ dV, int n_keys, int T, int Fp, int d, float scale) {
   using G = MkGeom<DP>;
@@ -229,6 +257,7 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
   const int kblocks = 2 * tilesC;  // (whole tiles: every row of d_k / d_v is written)
   const int kb = blockIdx.x % kblocks, b = blockIdx.x / kblocks;
   const int nv = mk_count(n_valid, b, n_keys);
+  const int nq = NQ ? mk_count(n_q_valid, b, T) : T;  // (uniform over the workgroup)
   const int key0 = 16 * kb;
   if (key0 >= nv) {  // (uniform over the workgroup)
     for (int i = tid; i < 16 * (Fp >> 2); i += 256) {
@@ -245,9 +274,9 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) aK[dt] = aV[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const bool key_ok = key0 + c < nv;
-  for (int q0 = wave * 16; q0 < T; q0 += 64) {
+  for (int q0 = wave * 16; q0 < nq; q0 += 64) {
     const int q = q0 + c;
-    const bool live = q < T;
+    const bool live = q < nq;
     // S[q = q0 + 4 g + i][key = c] and dP alike; D and the log-sum-exp of the lane's query c on the way
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
     f32x4 dd = {0.f, 0.f, 0.f, 0.f};  // dO O^T [row = query 4 g + i][column = query c]: D on its diagonal, summed as dP is
@@ -267,7 +296,7 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
       // (row 4 g + i of column 4 g + i: element i of the lane of this group whose column is 4 g + i; lane 4 g + i holds query
       // q0 + 4 g + i as its column)
       const float Di = __shfl(dd[i], 20 * g + i), Li = __shfl(Lc, 4 * g + i);
-      pr[i] = (key_ok && q0 + 4 * g + i < T) ? expf(s[i] * scale - Li) : 0.f;
+      pr[i] = (key_ok && q0 + 4 * g + i < nq) ? expf(s[i] * scale - Li) : 0.f;
       ds[i] = scale * pr[i] * (dp[i] - Di);
     }
 #pragma unroll
@@ -276,7 +305,7 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
         const int f = 16 * dt + c;
-        const bool ok = qj < T && f < d;
+        const bool ok = qj < nq && f < d;
         const size_t at = mk_pt(b, tilesT, Fp, ok ? qj : 0, ok ? (f & ~3) : 0) + (f & 3);
         aV[dt] = mk_mfma(ok ? dO[at] : 0.f, pr[j], aV[dt]);  // A[row = f][k = query 4 g + j]
         aK[dt] = mk_mfma(ok ? Q[at] : 0.f, ds[j], aK[dt]);
@@ -366,8 +395,9 @@ static int masked_attn_check(const void* q, const void* k, const void* v, const 
     }                       \
   } while (0)
 
-extern "C" int npf_masked_attn_fwd(const float* q, const float* k, const float* v, const int32_t* n_valid, int32_t n_tasks,
-                                   int32_t n_keys, int32_t n_queries, int32_t d, float scale, float* out, float* lse, void* stream) {
+static int masked_attn_fwd(const float* q, const float* k, const float* v, const int32_t* n_valid, const int32_t* n_q_valid,
+                           int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d, float scale, float* out, float* lse,
+                           void* stream) {
   const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
   if (rc != NPF_OK) return rc;
   if (!out || mk_misaligned(out)) return NPF_EINVAL;
@@ -375,17 +405,25 @@ extern "C" int npf_masked_attn_fwd(const float* q, const float* k, const float* 
   const int Fp = npf::round_up(d, 32);
   const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64)), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define MK_FWD(DP) \
-  hipLaunchKernelGGL(npf::masked_attn_fwd_kernel<DP>, grid, block, 0, st, q, k, v, n_valid, out, lse, n_keys, n_queries, Fp, d, scale)
-  MK_DISPATCH(MK_FWD);
+#define MK_FWD_I(DP, NQ)                                                                                                          \
+  hipLaunchKernelGGL((npf::masked_attn_fwd_kernel<DP, NQ>), grid, block, 0, st, q, k, v, n_valid, n_q_valid, out, lse, n_keys, \
+                     n_queries, Fp, d, scale)
+#define MK_FWD(DP) MK_FWD_I(DP, false)
+#define MK_FWD_NQ(DP) MK_FWD_I(DP, true)
+  if (n_q_valid)
+    MK_DISPATCH(MK_FWD_NQ);
+  else
+    MK_DISPATCH(MK_FWD);
+#undef MK_FWD_NQ
 #undef MK_FWD
+#undef MK_FWD_I
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }
 
-extern "C" int npf_masked_attn_bwd(const float* q, const float* k, const float* v, const int32_t* n_valid, const float* out,
-                                   const float* d_out, const float* lse, int32_t n_tasks, int32_t n_keys, int32_t n_queries,
-                                   int32_t d, float scale, float* d_q, float* d_k, float* d_v, void* stream) {
+static int masked_attn_bwd(const float* q, const float* k, const float* v, const int32_t* n_valid, const int32_t* n_q_valid,
+                           const float* out, const float* d_out, const float* lse, int32_t n_tasks, int32_t n_keys,
+                           int32_t n_queries, int32_t d, float scale, float* d_q, float* d_k, float* d_v, void* stream) {
   const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
   if (rc != NPF_OK) return rc;
   if (!out || !d_out || !lse || !d_q || (n_keys > 0 && (!d_k || !d_v))) return NPF_EINVAL;
@@ -396,23 +434,63 @@ extern "C" int npf_masked_attn_bwd(const float* q, const float* k, const float* 
   hipStream_t st = (hipStream_t)stream;
   if (n_queries > 0) {
     const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64));
-#define MK_DQ(DP)                                                                                                                  \
-  hipLaunchKernelGGL(npf::masked_attn_dq_kernel<DP>, grid, block, 0, st, q, k, v, n_valid, out, d_out, lse, d_q, n_keys, n_queries, \
-                     Fp, d, scale)
-    MK_DISPATCH(MK_DQ);
+#define MK_DQ_I(DP, NQ)                                                                                                               \
+  hipLaunchKernelGGL((npf::masked_attn_dq_kernel<DP, NQ>), grid, block, 0, st, q, k, v, n_valid, n_q_valid, out, d_out, lse, d_q, \
+                     n_keys, n_queries, Fp, d, scale)
+#define MK_DQ(DP) MK_DQ_I(DP, false)
+#define MK_DQ_NQ(DP) MK_DQ_I(DP, true)
+    if (n_q_valid)
+      MK_DISPATCH(MK_DQ_NQ);
+    else
+      MK_DISPATCH(MK_DQ);
+#undef MK_DQ_NQ
 #undef MK_DQ
+#undef MK_DQ_I
     NPF_CHECK_LAUNCH();
   }
   if (n_keys > 0) {  // (no queries: the walk over them is empty and the kernel stores the zeros)
     const dim3 grid((unsigned)n_tasks * (2 * ((n_keys + 31) / 32)));
-#define MK_DKV(DP)                                                                                                                \
-  hipLaunchKernelGGL(npf::masked_attn_dkv_kernel<DP>, grid, block, 0, st, q, k, v, n_valid, out, d_out, lse, d_k, d_v, n_keys, \
-                     n_queries, Fp, d, scale)
-    MK_DISPATCH(MK_DKV);
+#define MK_DKV_I(DP, NQ)                                                                                                            \
+  hipLaunchKernelGGL((npf::masked_attn_dkv_kernel<DP, NQ>), grid, block, 0, st, q, k, v, n_valid, n_q_valid, out, d_out, lse, d_k, \
+                     d_v, n_keys, n_queries, Fp, d, scale)
+#define MK_DKV(DP) MK_DKV_I(DP, false)
+#define MK_DKV_NQ(DP) MK_DKV_I(DP, true)
+    if (n_q_valid)
+      MK_DISPATCH(MK_DKV_NQ);
+    else
+      MK_DISPATCH(MK_DKV);
+#undef MK_DKV_NQ
 #undef MK_DKV
+#undef MK_DKV_I
     NPF_CHECK_LAUNCH();
   }
   return NPF_OK;
+}
+
+extern "C" int npf_masked_attn_fwd(const float* q, const float* k, const float* v, const int32_t* n_valid, int32_t n_tasks,
+                                   int32_t n_keys, int32_t n_queries, int32_t d, float scale, float* out, float* lse, void* stream) {
+  return masked_attn_fwd(q, k, v, n_valid, nullptr, n_tasks, n_keys, n_queries, d, scale, out, lse, stream);
+}
+
+extern "C" int npf_masked_attn_bwd(const float* q, const float* k, const float* v, const int32_t* n_valid, const float* out,
+                                   const float* d_out, const float* lse, int32_t n_tasks, int32_t n_keys, int32_t n_queries,
+                                   int32_t d, float scale, float* d_q, float* d_k, float* d_v, void* stream) {
+  return masked_attn_bwd(q, k, v, n_valid, nullptr, out, d_out, lse, n_tasks, n_keys, n_queries, d, scale, d_q, d_k, d_v, stream);
+}
+
+extern "C" int npf_masked_attn_fwd_nq(const float* q, const float* k, const float* v, const int32_t* n_valid,
+                                      const int32_t* n_q_valid, int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d,
+                                      float scale, float* out, float* lse, void* stream) {
+  if (!n_q_valid) return NPF_EINVAL;
+  return masked_attn_fwd(q, k, v, n_valid, n_q_valid, n_tasks, n_keys, n_queries, d, scale, out, lse, stream);
+}
+
+extern "C" int npf_masked_attn_bwd_nq(const float* q, const float* k, const float* v, const int32_t* n_valid,
+                                      const int32_t* n_q_valid, const float* out, const float* d_out, const float* lse,
+                                      int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d, float scale, float* d_q,
+                                      float* d_k, float* d_v, void* stream) {
+  if (!n_q_valid) return NPF_EINVAL;
+  return masked_attn_bwd(q, k, v, n_valid, n_q_valid, out, d_out, lse, n_tasks, n_keys, n_queries, d, scale, d_q, d_k, d_v, stream);
 }
 
 extern "C" int npf_masked_mean_fwd(const float* R_pt, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* out,

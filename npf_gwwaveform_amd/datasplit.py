@@ -59,7 +59,11 @@ class GetRandomIndcs:
     ``random`` is not touched).  The indices come back padded to the largest possible count ``_point_count(b, n)`` -- a
     shape that does not change from batch to batch, which is what a captured graph needs -- and the counts of the last
     draw are in ``last_counts`` (int64 [batch_size]): row ``i`` uses its first ``last_counts[i]`` indices, the model takes
-    the counts as ``n_cntxt``.  The default keeps the reference's behaviour."""
+    the counts as ``n_cntxt`` (``n_trgt`` when it is the targets getter).  The default keeps the reference's behaviour.
+
+    ``n_points`` (call argument, with ``is_per_task=True`` only): an integer device tensor [batch_size] for a padded DATA SET --
+    row ``i`` has ``n_points[i]`` real points out of ``n_possible_points``.  Its indices are drawn among its first
+    ``n_points[i]`` points only and its count is clamped to ``n_points[i]``; all on the device, no host sync."""
 
     def __init__(self, a=0.1, b=0.5, is_batch_share=False, range_indcs=None, is_ensure_one=False,
                  is_beta_binomial=False, proba_uniform=0, is_per_task=False):
@@ -88,7 +92,9 @@ class GetRandomIndcs:
             n = 1
         return n
 
-    def __call__(self, batch_size, n_possible_points, device=None, generator: Optional[torch.Generator] = None):
+    def __call__(self, batch_size, n_possible_points, device=None, generator: Optional[torch.Generator] = None, n_points=None):
+        if n_points is not None and (not self.is_per_task or self.is_batch_share or self.range_indcs is not None):
+            raise NotImplementedError("n_points (a padded data set) needs is_per_task=True and neither is_batch_share nor range_indcs")
         if self.range_indcs is not None:
             n_possible_points = self.range_indcs[1] - self.range_indcs[0]
         if self.is_per_task:
@@ -96,6 +102,9 @@ class GetRandomIndcs:
             if self.is_ensure_one:
                 lo, n = max(lo, 1), max(n, 1)
             self.last_counts = torch.randint(lo, n + 1, (batch_size,), device=device, generator=generator)
+            if n_points is not None:
+                n_points = n_points.to(device=self.last_counts.device, dtype=torch.int64).clamp(0, n_possible_points)
+                self.last_counts = torch.minimum(self.last_counts, n_points)
         else:
             n = self.n_indcs(n_possible_points)
         if self.is_batch_share:
@@ -104,6 +113,9 @@ class GetRandomIndcs:
         else:
             # an independent uniformly random subset (in random order) per row
             noise = torch.rand(batch_size, n_possible_points, device=device, generator=generator)
+            if n_points is not None:  # (the padding points sort last: the first min(count, n_points) indices of a row are real points)
+                beyond = torch.arange(n_possible_points, device=noise.device).unsqueeze(0) >= n_points.unsqueeze(1)
+                noise = noise.masked_fill(beyond, float("inf"))
             indcs = noise.argsort(dim=1)[:, :n]
         if self.range_indcs is not None:
             indcs = indcs + self.range_indcs[0]
@@ -115,6 +127,10 @@ class CntxtTrgtGetter:
     ``X_cntxt, Y_cntxt, X_trgt, Y_trgt`` -- and, behind a ``contexts_getter`` with ``is_per_task=True``, a fifth value
     ``n_cntxt`` (int64 [B], on the device): the context comes padded to a fixed number of rows, task ``b`` owns the first
     ``n_cntxt[b]`` and the rows beyond are zero-filled; :meth:`batch` returns the same as the dict a model / ``Trainer.step`` takes.
+    A ``targets_getter`` with ``is_per_task=True`` does the same for the targets: a sixth value ``n_trgt`` (the fifth is None when
+    the contexts are not per-task), targets zero-filled beyond the count.  ``n_points=n`` (an integer device tensor [B]) splits a
+    padded DATA SET, task ``b`` having ``n[b]`` real points out of ``X.shape[1]``: the per-task getters draw among those only,
+    and with ``targets_getter=get_all_indcs`` the batch carries ``n_trgt = n``.  Nothing here reads a count on the host.
     Same constructor arguments, call signature and overridable hooks
     (``preprocess_context``, ``add_cntxts_to_trgts``, ``getter_inputs``, ``select``) as the reference; the work is
     two steps: :meth:`indices` decides which points go where (device-side draws unless the caller supplies them),
@@ -125,7 +141,7 @@ class CntxtTrgtGetter:
         self.targets_getter = targets_getter
         self.is_add_cntxts_to_trgts = is_add_cntxts_to_trgts
 
-    def indices(self, X, context_indcs=None, target_indcs=None):
+    def indices(self, X, context_indcs=None, target_indcs=None, n_points=None):
         """(context indices, target indices, were any supplied by the caller) for the batch ``X``."""
         batch_size, num_points = self.getter_inputs(X)
         supplied = not (context_indcs is None and target_indcs is None)
@@ -133,6 +149,9 @@ class CntxtTrgtGetter:
         for given, getter in ((context_indcs, self.contexts_getter), (target_indcs, self.targets_getter)):
             if given is not None:
                 drawn.append(given)
+                continue
+            if n_points is not None and getattr(getter, "is_per_task", False):
+                drawn.append(getter(batch_size, num_points, device=X.device, n_points=n_points))
                 continue
             try:
                 drawn.append(getter(batch_size, num_points, device=X.device))
@@ -143,25 +162,47 @@ class CntxtTrgtGetter:
             trg = self.add_cntxts_to_trgts(num_points, trg, ctx)
         return ctx, trg, supplied
 
-    def __call__(self, X, y=None, context_indcs=None, target_indcs=None, is_return_indcs=False):
-        ctx, trg, supplied = self.indices(X, context_indcs, target_indcs)
+    def __call__(self, X, y=None, context_indcs=None, target_indcs=None, is_return_indcs=False, n_points=None):
+        per_task_c = context_indcs is None and getattr(self.contexts_getter, "is_per_task", False)
+        per_task_t = target_indcs is None and getattr(self.targets_getter, "is_per_task", False)
+        all_t = target_indcs is None and self.targets_getter is get_all_indcs
+        if self.is_add_cntxts_to_trgts and (per_task_t or n_points is not None):
+            raise NotImplementedError("is_add_cntxts_to_trgts is not implemented with per-task targets or n_points")
+        if n_points is not None:
+            if not isinstance(n_points, torch.Tensor) or n_points.dtype not in (torch.int32, torch.int64) \
+                    or tuple(n_points.shape) != (X.shape[0],):
+                raise ValueError(f"n_points must be an integer tensor of shape [{X.shape[0]}] (the real points of every task)")
+            if not (per_task_c and (per_task_t or all_t)):
+                raise NotImplementedError("n_points needs a contexts getter with is_per_task=True and, as targets getter, "
+                                          "get_all_indcs or a getter with is_per_task=True")
+            n_points = n_points.to(device=X.device, dtype=torch.int64).clamp(0, X.shape[1])
+        ctx, trg, supplied = self.indices(X, context_indcs, target_indcs, n_points=n_points)
         X_for_context = self.preprocess_context(X)
         if is_return_indcs:
             return ctx, X_for_context, trg, X
         # caller-supplied indices are range-checked (one host sync); the getters' own draws are in range by construction
         Xc, Yc = self.select(X_for_context, y, ctx, validate=supplied)
         Xt, Yt = self.select(X, y, trg, validate=supplied)
-        if context_indcs is None and getattr(self.contexts_getter, "is_per_task", False):
+        n_cntxt = n_trgt = None
+        if per_task_c:
             n_cntxt = self.contexts_getter.last_counts
             pad = (torch.arange(Xc.shape[1], device=Xc.device).unsqueeze(0) >= n_cntxt.unsqueeze(1)).unsqueeze(-1)
-            return Xc.masked_fill(pad, 0.0), Yc.masked_fill(pad, 0.0), Xt, Yt, n_cntxt
+            Xc, Yc = Xc.masked_fill(pad, 0.0), Yc.masked_fill(pad, 0.0)
+        if per_task_t or (n_points is not None and all_t):
+            n_trgt = self.targets_getter.last_counts if per_task_t else n_points
+            pad = (torch.arange(Xt.shape[1], device=Xt.device).unsqueeze(0) >= n_trgt.unsqueeze(1)).unsqueeze(-1)
+            Xt, Yt = Xt.masked_fill(pad, 0.0), Yt.masked_fill(pad, 0.0)
+        if n_trgt is not None:
+            return Xc, Yc, Xt, Yt, n_cntxt, n_trgt
+        if n_cntxt is not None:
+            return Xc, Yc, Xt, Yt, n_cntxt
         return Xc, Yc, Xt, Yt
 
     def batch(self, X, y=None, **kwargs) -> dict:
         """The split as the dict ``Trainer.step`` / ``eval_loglike`` take: ``X_cntxt, Y_cntxt, X_trgt, Y_trgt`` and, with a
-        per-task contexts getter, ``n_cntxt``."""
+        per-task contexts getter, ``n_cntxt``; with a per-task targets getter or ``n_points`` (see the class), ``n_trgt``."""
         out = self(X, y, **kwargs)
-        return dict(zip(("X_cntxt", "Y_cntxt", "X_trgt", "Y_trgt", "n_cntxt"), out))
+        return {k: v for k, v in zip(("X_cntxt", "Y_cntxt", "X_trgt", "Y_trgt", "n_cntxt", "n_trgt"), out) if v is not None}
 
     # ---- hooks of the reference ---------------------------------------------------------------------------------
     def preprocess_context(self, X):

@@ -15,7 +15,7 @@ def eval_loglike(model: torch.nn.Module, criterion: torch.nn.Module, batches: It
     """Log-likelihood of every task of every batch, in order, as one numpy vector.
 
     ``batches`` yields dicts ``X_cntxt, Y_cntxt, X_trgt, Y_trgt`` of device tensors (what ``CntxtTrgtGetter``
-    produces), optionally with the per-task context sizes ``n_cntxt`` of a padded batch.  Like the reference: the seed is set first (same latent noise and -- if the batches are generated
+    produces), optionally with the per-task context / target sizes ``n_cntxt`` / ``n_trgt`` of a padded batch.  Like the reference: the seed is set first (same latent noise and -- if the batches are generated
     lazily -- the same context / target draws on every call), model and criterion run in evaluation mode (so the
     criterion is the log-mean-exp over ``n_z_samples_test`` latent samples), the criterion's reduction is switched
     off for the call and restored afterwards, and the sign is flipped (log-likelihood, not loss)."""
@@ -35,7 +35,7 @@ def eval_loglike(model: torch.nn.Module, criterion: torch.nn.Module, batches: It
     try:
         with torch.no_grad():
             for batch in batches:
-                extra = {"n_cntxt": batch["n_cntxt"]} if batch.get("n_cntxt") is not None else {}
+                extra = {k: batch[k] for k in ("n_cntxt", "n_trgt") if batch.get(k) is not None}
                 pred = model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"], **extra)
                 out.append(-criterion(pred, batch["Y_trgt"]))
     finally:

@@ -140,11 +140,70 @@ class _GaussHeadFn(torch.autograd.Function):
         return d_suff, None, None, None, None
 
 
-def gauss_head(suff: torch.Tensor, Y: Optional[torch.Tensor], dy: int, homoskedastic: bool, want_dist: bool = True):
+class _MaskedGaussHeadFn(torch.autograd.Function):
+    """``_GaussHeadFn`` over padded targets: row ``r`` owns its first ``n_valid[r % n_tasks]`` points (``npf_masked_gauss_head_fwd`` /
+    ``_bwd``).  Beyond the count: loc = 0, scale = 1, nothing in ``sum_log_prob``, zero rows in the gradient."""
+
+    @staticmethod
+    def forward(ctx, suff, Y, n_valid, dy, homosk, want_dist):
+        n_rows, pts, two_dy = suff.shape
+        n_tasks = n_valid.shape[0]
+        assert two_dy == 2 * dy and n_rows % n_tasks == 0
+        suff = suff.contiguous()
+        loc = scale = None
+        if want_dist:
+            loc = torch.empty((n_rows, pts, dy), dtype=torch.float32, device=suff.device)
+            scale = torch.empty_like(loc)
+        slp = None
+        n_y = 0
+        if Y is not None:
+            Y = Y.contiguous()
+            n_y = Y.shape[0]
+            assert Y.shape[1:] == (pts, dy) and n_rows % n_y == 0 and n_y % n_tasks == 0
+            slp = torch.empty((n_rows,), dtype=torch.float32, device=suff.device)
+        elif not want_dist:
+            raise ValueError("a loss-only head launch needs the targets")
+        L.check(L.load().npf_masked_gauss_head_fwd(L.ptr(suff), _iptr(n_valid), n_tasks, n_rows, pts, dy, int(homosk), L.ptr(Y), n_y,
+                                                   L.ptr(loc), L.ptr(scale), L.ptr(slp), L.stream_ptr()), "npf_masked_gauss_head_fwd")
+        ctx.save_for_backward(suff, loc, scale, Y, n_valid)
+        ctx.cfg = (dy, homosk)
+        empty = suff.new_zeros((0,))
+        outs = [loc if want_dist else empty, scale if want_dist else empty, slp if slp is not None else suff.new_zeros((n_rows,))]
+        nd = ([] if want_dist else [outs[0], outs[1]]) + ([] if slp is not None else [outs[2]])
+        if nd:
+            ctx.mark_non_differentiable(*nd)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, d_loc, d_scale, d_slp):
+        suff, loc, scale, Y, n_valid = ctx.saved_tensors
+        dy, homosk = ctx.cfg
+        n_rows, pts, _ = suff.shape
+        d_suff = torch.empty_like(suff)  # (written whole: zeros beyond the count)
+        c = lambda t: t.contiguous() if t is not None else None  # noqa: E731
+        if loc is None:
+            d_loc = d_scale = None
+        L.check(L.load().npf_masked_gauss_head_bwd(L.ptr(suff), L.ptr(loc), L.ptr(scale), _iptr(n_valid), n_valid.shape[0], n_rows,
+                                                   pts, dy, int(homosk), L.ptr(Y), Y.shape[0] if Y is not None else 0,
+                                                   L.ptr(c(d_loc)), L.ptr(c(d_scale)), L.ptr(c(d_slp)) if Y is not None else None,
+                                                   L.ptr(d_suff), L.stream_ptr()), "npf_masked_gauss_head_bwd")
+        return d_suff, None, None, None, None, None
+
+
+def gauss_head(suff: torch.Tensor, Y: Optional[torch.Tensor], dy: int, homoskedastic: bool, want_dist: bool = True,
+               n_valid: Optional[torch.Tensor] = None):
     """(loc, scale, sum_log_prob) from the raw decoder output ``suff`` [rows, pts, 2*dy]
     (npf/neuralproc/base.py:350-365; losses.py:18-24).  ``sum_log_prob`` [rows] is the
     log-likelihood of ``Y`` [rows or B, pts, dy] summed over targets and y-dims.  ``want_dist=False``: a
-    loss-only launch -- loc and scale come back empty and nothing of size [rows, pts, dy] is written."""
+    loss-only launch -- loc and scale come back empty and nothing of size [rows, pts, dy] is written.
+    ``n_valid``: device integer tensor [n_tasks] (``rows`` a multiple of it, row ``r`` is task ``r % n_tasks``), the number of real
+    points of every task of a padded batch: sums and the homoskedastic pooling cover the rows below the count only, beyond it
+    loc = 0 and scale = 1, ``Y`` there is never read and the gradient rows are zeros (``npf_masked_gauss_head_fwd`` / ``_bwd``)."""
+    if n_valid is not None:
+        n_tasks = n_valid.shape[0] if isinstance(n_valid, torch.Tensor) and n_valid.dim() == 1 else suff.shape[0]
+        if suff.shape[0] % max(n_tasks, 1) != 0 or n_tasks == 0:
+            raise ValueError(f"n_valid has {n_tasks} counts, the head {suff.shape[0]} rows (not a multiple)")
+        return _MaskedGaussHeadFn.apply(suff, Y, counts_i32(n_valid, n_tasks), dy, homoskedastic, want_dist)
     return _GaussHeadFn.apply(suff, Y, dy, homoskedastic, want_dist)
 
 
@@ -380,7 +439,7 @@ class _MaskedAttnFn(torch.autograd.Function):
     ``_bwd``; DotAttender.forward, npf/architectures/attention.py:129-164,204-220, of the batch cut per task)."""
 
     @staticmethod
-    def forward(ctx, q_pt, k_pt, v_pt, n_valid, n_tasks, n_keys, n_queries, d, scale):
+    def forward(ctx, q_pt, k_pt, v_pt, n_valid, n_tasks, n_keys, n_queries, d, scale, n_q_valid=None):
         from . import chain as CH
 
         q_pt, k_pt, v_pt = q_pt.contiguous(), k_pt.contiguous(), v_pt.contiguous()
@@ -390,16 +449,22 @@ class _MaskedAttnFn(torch.autograd.Function):
         if CH.PROFILE is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        L.check(L.load().npf_masked_attn_fwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), n_tasks, n_keys, n_queries, d,
-                                             float(scale), L.ptr(out), L.ptr(lse) if lse is not None else None, L.stream_ptr()),
-                "npf_masked_attn_fwd")
+        if n_q_valid is not None:  # (padded queries as well: the instances that skip them)
+            L.check(L.load().npf_masked_attn_fwd_nq(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), _iptr(n_q_valid), n_tasks,
+                                                    n_keys, n_queries, d, float(scale), L.ptr(out),
+                                                    L.ptr(lse) if lse is not None else None, L.stream_ptr()), "npf_masked_attn_fwd_nq")
+        else:
+            L.check(L.load().npf_masked_attn_fwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), n_tasks, n_keys, n_queries, d,
+                                                 float(scale), L.ptr(out), L.ptr(lse) if lse is not None else None, L.stream_ptr()),
+                    "npf_masked_attn_fwd")
         if CH.PROFILE is not None:
             ev1.record()
             CH.PROFILE.append(("masked_attn_fwd_kernel", 4 * n_tasks * n_queries * n_keys * d, ev0, ev1,
                                4 * pad32(d) * n_tasks * (2 * n_queries + 2 * n_keys), "masked attention (flops at full counts)"))
         ctx.geom = (n_tasks, n_keys, n_queries, d, float(scale))
+        ctx.has_nq = n_q_valid is not None
         if train:
-            ctx.save_for_backward(q_pt, k_pt, v_pt, n_valid, out, lse)
+            ctx.save_for_backward(q_pt, k_pt, v_pt, n_valid, out, lse, *((n_q_valid,) if ctx.has_nq else ()))
         return out
 
     @staticmethod
@@ -407,30 +472,41 @@ class _MaskedAttnFn(torch.autograd.Function):
         from . import chain as CH
 
         n_tasks, n_keys, n_queries, d, scale = ctx.geom
-        q_pt, k_pt, v_pt, n_valid, out, lse = ctx.saved_tensors
+        q_pt, k_pt, v_pt, n_valid, out, lse = ctx.saved_tensors[:6]
         g = g.contiguous()
         dq, dk, dv = torch.empty_like(q_pt), torch.empty_like(k_pt), torch.empty_like(v_pt)  # (written whole)
         if CH.PROFILE is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        L.check(L.load().npf_masked_attn_bwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), L.ptr(out), L.ptr(g), L.ptr(lse),
-                                             n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.stream_ptr()),
-                "npf_masked_attn_bwd")
+        if ctx.has_nq:
+            L.check(L.load().npf_masked_attn_bwd_nq(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), _iptr(ctx.saved_tensors[6]),
+                                                    L.ptr(out), L.ptr(g), L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq),
+                                                    L.ptr(dk), L.ptr(dv), L.stream_ptr()), "npf_masked_attn_bwd_nq")
+        else:
+            L.check(L.load().npf_masked_attn_bwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), L.ptr(out), L.ptr(g),
+                                                 L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk), L.ptr(dv),
+                                                 L.stream_ptr()), "npf_masked_attn_bwd")
         if CH.PROFILE is not None:
             ev1.record()
             CH.PROFILE.append(("masked_attn_bwd_kernels", 16 * n_tasks * n_queries * n_keys * d, ev0, ev1,
                                4 * pad32(d) * n_tasks * (6 * n_queries + 4 * n_keys), "masked attention backward (flops at full counts)"))
-        return dq, dk, dv, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def masked_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, n_keys: int,
-                     n_queries: int, d: int, scale: float) -> torch.Tensor:
+                     n_queries: int, d: int, scale: float, n_q_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """PT32 [n_tasks, n_queries, d]: scaled-dot attention of every task's queries over the first ``n_valid[task]`` of its ``n_keys``
     keys / values (zeros where a task has none).  ``n_valid``: device int32 / int64 [n_tasks], read by the kernel only -- no host
-    sync, so the call can be captured in a graph and replayed with new counts.  ``d`` % 4 == 0, ``d`` <= 256, any ``n_keys``."""
+    sync, so the call can be captured in a graph and replayed with new counts.  ``d`` % 4 == 0, ``d`` <= 256, any ``n_keys``.
+    ``n_q_valid``: the same for the queries (padded targets): the rows of the result at and beyond ``n_q_valid[task]`` are zeros, the
+    queries there are never read and get a zero gradient, and the kernels skip them (``npf_masked_attn_fwd_nq`` / ``_bwd_nq``); the
+    rows below the counts are bit-identical to the call without it."""
     if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
         raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
-    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale)
+    if n_q_valid is None:
+        return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale)
+    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale,
+                               counts_i32(n_q_valid, n_tasks, "n_q_valid"))
 
 
 class _MaskedMeanFn(torch.autograd.Function):

@@ -47,12 +47,15 @@ class HeadDistribution(Independent):
     ``loc`` / ``scale`` are only materialised ([n_z, B, T, y_dim] each, one ``npf_gauss_head_fwd`` launch) when
     ``base_dist`` (or anything that needs it: ``mean``, ``log_prob``, ``sample`` ...) is first touched.  The
     training and evaluation objectives never do: :meth:`sum_log_prob` is a loss-only launch that writes one float
-    per (z-sample, task)."""
+    per (z-sample, task).
 
-    def __init__(self, suff, y_dim, homoskedastic, n_z, B, T):
+    ``n_trgt`` (device int32 [B]): the targets are padded, task ``b`` owns its first ``n_trgt[b]`` rows.  ``sum_log_prob`` and the
+    homoskedastic pooling then cover those rows only, and the rows beyond have ``loc = 0``, ``scale = 1``."""
+
+    def __init__(self, suff, y_dim, homoskedastic, n_z, B, T, n_trgt=None):
         torch.distributions.Distribution.__init__(self, torch.Size((n_z, B, T)), torch.Size((y_dim,)), validate_args=False)
         self.reinterpreted_batch_ndims = 1
-        self._suff, self._y_dim, self._homosk = suff, y_dim, homoskedastic
+        self._suff, self._y_dim, self._homosk, self._n_trgt = suff, y_dim, homoskedastic, n_trgt
         self._base = None
         self._slp = None  # (targets, [n_z, B] sum of log-probabilities) of the last sum_log_prob call
 
@@ -60,7 +63,7 @@ class HeadDistribution(Independent):
     def base_dist(self):
         if self._base is None:
             n_z, B, T = self.batch_shape
-            loc, scale, _ = FN.gauss_head(self._suff, None, self._y_dim, self._homosk)
+            loc, scale, _ = FN.gauss_head(self._suff, None, self._y_dim, self._homosk, n_valid=self._n_trgt)
             self._base = Normal(loc.view(n_z, B, T, self._y_dim), scale.view(n_z, B, T, self._y_dim), validate_args=False)
         return self._base
 
@@ -68,7 +71,8 @@ class HeadDistribution(Independent):
         """sum_t log p(y_t) -> [n_z, B] (npf/losses.py:18-24), fused with the head in one loss-only launch."""
         if self._slp is None or self._slp[0] is not Y_trgt:
             n_z, B, _ = self.batch_shape
-            _, _, slp = FN.gauss_head(self._suff, Y_trgt.contiguous(), self._y_dim, self._homosk, want_dist=False)
+            _, _, slp = FN.gauss_head(self._suff, Y_trgt.contiguous(), self._y_dim, self._homosk, want_dist=False,
+                                      n_valid=self._n_trgt)
             self._slp = (Y_trgt, slp.view(n_z, B))
         return self._slp[1]
 
@@ -127,7 +131,7 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         return d
 
     # ------------------------------------------------------------------ forward
-    def forward(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt=None, n_cntxt=None):
+    def forward(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt=None, n_cntxt=None, n_trgt=None):
         """Same contract as base.py:177-239: returns ``(p_yCc, z_samples, q_zCc, q_zCct)``.
 
         ``n_cntxt``: per-task context sizes of a PADDED batch -- an integer device tensor [B] (int32 or int64), task ``b`` uses
@@ -136,16 +140,30 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         in a graph is replayed with new counts.  The rows beyond the count have no influence on any output or gradient, but the
         training-time range check covers them too: padding must be finite and inside [-1, 1] (fill it with zeros).  ``X_cntxt``
         with zero rows behaves as without ``n_cntxt``.  Not implemented with ``n_cntxt``: self-attention context encoders
-        (``is_self_attn=True``) and the bf16 compute mode."""
+        (``is_self_attn=True``) and the bf16 compute mode.
+
+        ``n_trgt``: the same for the targets -- an integer device tensor [B], task ``b`` owns the rows ``X_trgt[b, :n_trgt[b]]`` /
+        ``Y_trgt[b, :n_trgt[b]]``.  For every row ``t < n_trgt[b]`` everything returned equals what the single-task batch cut to
+        those target rows (and, with ``n_cntxt``, those context rows) returns; the per-task loss (the returned distribution carries
+        the counts: ``criterion(out, Y_trgt)`` as always) and every parameter gradient equal those of the cut batch.  Rows
+        ``t >= n_trgt[b]`` have no influence on any row below the count, on the loss or on any gradient; their ``loc`` is 0 and
+        their ``scale`` 1.  The padding must be finite and, in training, inside [-1, 1] (fill it with zeros).  ``n_trgt[b] == 0``
+        is allowed: that task's log-likelihood is 0 and it contributes no gradient.  Read by the kernels only, like ``n_cntxt``:
+        one captured step serves every mix of both counts.  Without ``n_cntxt`` the step keeps its path (padded targets are just
+        points to the per-point stages); what ties a task's targets together -- the head and the loss, the homoskedastic pooling,
+        the target-side mean of the latent path -- reads the counts.  With ``n_cntxt`` the masked attention also skips the
+        queries beyond the count.  Not implemented with ``n_trgt``: ``is_self_attn=True`` and the bf16 compute mode."""
         if n_cntxt is not None:
             n_cntxt = self._check_n_cntxt(n_cntxt, X_cntxt)
+        if n_trgt is not None:
+            n_trgt = self._check_n_trgt(n_trgt, X_trgt)
         self._validate_inputs(X_cntxt, Y_cntxt, X_trgt, Y_trgt)
         B, C, _ = X_cntxt.shape
         T = X_trgt.shape[1]
         if T == 0:
             raise ValueError("no target points")
         if n_cntxt is not None and C > 0:
-            return self._forward_padded(X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt)
+            return self._forward_padded(X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt, n_trgt)
         from . import chain as _chain
 
         fused_t = self._fused_target_side(C, T)
@@ -173,13 +191,13 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         else:
             Xt_pt = self._xenc_pt(X_trgt)
         if self.encoded_path in ["latent", "both"]:
-            z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T)
+            z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T, n_trgt=n_trgt)
         else:
             z_samples, q_zCc, q_zCct = None, None, None
         if self.encoded_path == "latent":
             R = None
         suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T)  # [n_z * B, T, 2 dy]
-        p_yCc = self._head(suff, Y_trgt, B, T)
+        p_yCc = self._head(suff, Y_trgt, B, T, n_trgt=n_trgt)
         return p_yCc, z_samples, q_zCc, q_zCct
 
     def _check_n_cntxt(self, n_cntxt, X_cntxt):
@@ -195,11 +213,25 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
             raise ValueError(f"n_cntxt lives on {n.device}, the batch on {X_cntxt.device}")
         return n
 
-    def _forward_padded(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt):
-        """``forward`` over a padded batch (``n_cntxt``: device int32 [B]).  The per-point stages -- x-encoder, XY-encoder, over all
+    def _check_n_trgt(self, n_trgt, X_trgt):
+        """The per-task target sizes as a device int32 [B] tensor; refuses what the padded path does not implement."""
+        from . import chain as _chain
+
+        if getattr(self, "is_self_attn", False):
+            raise NotImplementedError("n_trgt is not implemented for self-attention context encoders (is_self_attn=True)")
+        if _chain.COMPUTE_DTYPE != "fp32":
+            raise NotImplementedError("n_trgt is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
+        n = FN.counts_i32(n_trgt, X_trgt.shape[0], "n_trgt")
+        if n.device != X_trgt.device:
+            raise ValueError(f"n_trgt lives on {n.device}, the batch on {X_trgt.device}")
+        return n
+
+    def _forward_padded(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt, n_trgt=None):
+        """``forward`` over a padded batch (``n_cntxt``: device int32 [B]; ``n_trgt``: the same for the targets, or None).  The per-point stages -- x-encoder, XY-encoder, over all
         rows of the padded context -- and the decoder keep the launches of an unfused step; what ties the points of a task together
         (attention over the context, the mean over it) runs on the masked kernels (csrc/masked_kernels.hip).  The fused target
-        side (x6.target_side) is not taken: its softmax has the key count as a launch argument."""
+        side (x6.target_side) is not taken: its softmax has the key count as a launch argument.  With ``n_trgt`` the masked attention
+        skips the queries beyond the count, and the head / the target-side mean of the latent path read it."""
         B, C, _ = X_cntxt.shape
         T = X_trgt.shape[1]
         if self._fused_context_side(C):
@@ -212,13 +244,13 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
             R = self._encode_globally_pt(Xc_pt, Y_cntxt, B, C, n_valid=n_cntxt)
         Xt_pt = self._xenc_pt(X_trgt)
         if self.encoded_path in ["latent", "both"]:
-            z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T, n_valid=n_cntxt)
+            z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T, n_valid=n_cntxt, n_trgt=n_trgt)
         else:
             z_samples, q_zCc, q_zCct = None, None, None
         if self.encoded_path == "latent":
             R = None
-        suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=n_cntxt)
-        return self._head(suff, Y_trgt, B, T), z_samples, q_zCc, q_zCct
+        suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=n_cntxt, n_q_valid=n_trgt)
+        return self._head(suff, Y_trgt, B, T, n_trgt=n_trgt), z_samples, q_zCc, q_zCct
 
     def _validate_inputs(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt):
         """base.py:241-247: features must be in [-1, 1] during training (the padding rows of a padded batch included)."""
@@ -289,8 +321,8 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         return self.xy_encoder.run_pt(ch, X_enc.t, X_enc.n_tasks, X_enc.pts,
                                       with_tr=self._attentive if with_tr is None else with_tr)
 
-    def _head(self, suff, Y_trgt, B, T):
-        return HeadDistribution(suff, self.y_dim, not self.is_heteroskedastic, suff.shape[0] // B, B, T)
+    def _head(self, suff, Y_trgt, B, T, n_trgt=None):
+        return HeadDistribution(suff, self.y_dim, not self.is_heteroskedastic, suff.shape[0] // B, B, T, n_trgt=n_trgt)
 
     def _decode_taskvec(self, Xt_pt, vec, B, T, n_rows):
         """decoder(X_trgt_enc, R_trgt) when R_trgt is one vector per (z-sample, task)
@@ -383,8 +415,9 @@ class LatentNeuralProcessFamily(NeuralProcessFamily):
             q_zCct, sampling_dist = None, q_zCc
         return sampling_dist.rsample([self.n_z_samples]), q_zCc, q_zCct
 
-    def _latent_path_pt(self, R, C, Xt_pt, Y_trgt, B, T, n_valid=None):
-        # (n_valid: the context sizes of a padded batch; the target-side encode below is over the targets and is not masked)
+    def _latent_path_pt(self, R, C, Xt_pt, Y_trgt, B, T, n_valid=None, n_trgt=None):
+        # (n_valid: the context sizes of a padded batch; n_trgt: the target sizes -- the target-side encode below pools over the
+        # first n_trgt[b] targets, zeros for a task without any, as encode_globally at zero points)
         q_zCc = self._latent_dist_from(self._lat_input(R, B) if n_valid is None else self._lat_input(R, B, n_valid=n_valid))
         if self.is_q_zCct and Y_trgt is not None:
             if Xt_pt is None:
@@ -393,12 +426,12 @@ class LatentNeuralProcessFamily(NeuralProcessFamily):
                 if self._fused_context_side(T):
                     from . import x6
 
-                    R_t = self._pool_pt(x6.context_side(self, self._X_trgt_raw, Y_trgt)[1], B)
+                    R_t = self._pool_pt(x6.context_side(self, self._X_trgt_raw, Y_trgt)[1], B, n_valid=n_trgt)
                 else:
-                    R_t = self._encode_globally_pt(self._xenc_pt(self._X_trgt_raw), Y_trgt, B, T)
+                    R_t = self._encode_globally_pt(self._xenc_pt(self._X_trgt_raw), Y_trgt, B, T, n_valid=n_trgt)
             else:
-                R_t = self._encode_globally_pt(Xt_pt, Y_trgt, B, T)
-            q_zCct = self._latent_dist_from(self._lat_input(R_t, B))
+                R_t = self._encode_globally_pt(Xt_pt, Y_trgt, B, T, n_valid=n_trgt)
+            q_zCct = self._latent_dist_from(self._lat_input(R_t, B) if n_trgt is None else self._lat_input(R_t, B, n_valid=n_trgt))
             sampling_dist = q_zCct
         else:
             q_zCct, sampling_dist = None, q_zCc
@@ -472,7 +505,7 @@ class CNP(NeuralProcessFamily):
             return FN.masked_mean(R_pts.t, n_valid, B, R_pts.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
         return FN.mean_agg(R_pts.t, R_pts.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None, n_q_valid=None):
         return self._decode_taskvec(Xt_pt, R.reshape(B, self.r_dim), B, T, B)
 
 
@@ -502,7 +535,7 @@ class LNP(LatentNeuralProcessFamily, CNP):
         n_z = z_samples.size(0)
         return self._rep_rows(z_samples, R, B).reshape(n_z, B, 1, self.r_dim).expand(n_z, B, T, self.r_dim)
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None, n_q_valid=None):
         n_z = z_samples.size(0)
         return self._decode_taskvec(Xt_pt, self._rep_rows(z_samples, R, B), B, T, n_z * B)
 
@@ -572,11 +605,12 @@ class AttnCNP(NeuralProcessFamily):
         """attnnp.py:105-116: no pooling, one representation per context point."""
         return R_pts
 
-    def _attend_padded(self, Xc_pt, R, Xt_pt, B, C, T, n_valid):
+    def _attend_padded(self, Xc_pt, R, Xt_pt, B, C, T, n_valid, n_q_valid=None):
         """PT32 [B, T, r]: attention of the targets over the first ``n_valid[b]`` context points of every task (attnnp.py:118-131
         on the batch cut per task).  A task without context gets zeros, as ``trgt_dependent_representation`` at C = 0 -- also
-        behind an attender whose learned layers would turn zero context vectors into something else."""
-        R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid)
+        behind an attender whose learned layers would turn zero context vectors into something else.  ``n_q_valid``: the target
+        sizes of a batch whose targets are padded too; the attention skips the queries beyond them."""
+        R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
         if not isinstance(self.attender, DotAttender):
             R_t = R_t * (n_valid > 0).to(R_t.dtype).view(B, 1, 1, 1, 1)
         return R_t
@@ -608,11 +642,11 @@ class AttnCNP(NeuralProcessFamily):
             ch.input_pt(self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, keys_tr=Xc_pt.tr, values_tr=R.tr), self.r_dim)
         return ch
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None, n_q_valid=None):
         if n_valid is not None:  # (a padded batch: masked attention, then the decoder as an unfused step runs it)
             from . import x6
 
-            R_t = self._attend_padded(Xc_pt, R, Xt_pt, B, C, T, n_valid)
+            R_t = self._attend_padded(Xc_pt, R, Xt_pt, B, C, T, n_valid, n_q_valid)
             if x6.decoder_side_usable(self, T):
                 return x6.decoder_side(self, R_t, Xt_pt.t, T)
             ch = Chain(B, T, Xt_pt.t.device, wg_per_task=True)
@@ -681,7 +715,7 @@ class AttnLNP(LatentNeuralProcessFamily, AttnCNP):
         return (type(self) is AttnLNP and self.n_z_samples == 1 and self.z_dim == self.r_dim
                 and x6.target_side_usable(self, C, T, latent_merge=True))
 
-    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None):
+    def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None, n_q_valid=None):
         n_z = z_samples.size(0)
         dev = z_samples.device
         W, b, r = self.r_z_merger.weight, self.r_z_merger.bias, self.r_dim
@@ -694,7 +728,7 @@ class AttnLNP(LatentNeuralProcessFamily, AttnCNP):
             from . import x6
 
             return x6.target_side(self, self._X_trgt_raw, Xc_pt, R, zb=zb)
-        R_pad = self._attend_padded(Xc_pt, R, Xt_pt, B, C, T, n_valid) if n_valid is not None else None
+        R_pad = self._attend_padded(Xc_pt, R, Xt_pt, B, C, T, n_valid, n_q_valid) if n_valid is not None else None
         if n_z == 1 and C > 0 and (R_pad is not None or not isinstance(self.attender, DotAttender)) and self.z_dim == self.r_dim:
             from . import x6
 

@@ -48,9 +48,9 @@ def get_exponential_decay_gamma(scheduling_factor, max_epochs):
     return (1 / scheduling_factor) ** (1 / max_epochs)
 
 
-def _n_cntxt_of(batch: dict) -> dict:
-    """The per-task context sizes of a padded batch as the model's keyword argument (nothing for a batch without them)."""
-    return {"n_cntxt": batch["n_cntxt"]} if batch.get("n_cntxt") is not None else {}
+def _counts_of(batch: dict) -> dict:
+    """The per-task context / target sizes of a padded batch as the model's keyword arguments (nothing for a batch without them)."""
+    return {k: batch[k] for k in ("n_cntxt", "n_trgt") if batch.get(k) is not None}
 
 
 class Trainer:
@@ -67,7 +67,8 @@ class Trainer:
         backward pass, which costs less than the host time of an eager step at these sizes; ``use_graph=False`` keeps the
         bucketed all-reduce overlapped with the backward pass).  Needs fixed batch shapes (a new shape or learning rate
         re-captures; ``n_captures`` counts them).  Batches whose context size changes keep ONE graph when they come padded to a
-        fixed number of rows with the per-task sizes as ``batch["n_cntxt"]`` (``GetRandomIndcs(is_per_task=True)``): the sizes
+        fixed number of rows with the per-task sizes as ``batch["n_cntxt"]`` (``GetRandomIndcs(is_per_task=True)``), and likewise
+        batches whose target size changes with ``batch["n_trgt"]`` (``CntxtTrgtGetter.batch(X, y, n_points=...)``): the sizes
         are a static input like the other batch tensors, only their shape is part of the graph's signature.  The range check of the inputs (base.py:241-247) stays in the step as a device reduction; its verdict
         is read at the next sync point: call :meth:`check_inputs` (e.g. once per epoch) to get the reference's ValueError."""
         self.model, self.criterion = model, criterion
@@ -204,7 +205,7 @@ class Trainer:
         for p in self.flat.params:
             p.grad = None
         self.reducer.reset()
-        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"], **_n_cntxt_of(batch))
+        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"], **_counts_of(batch))
         loss = self.criterion(out, batch["Y_trgt"])
         loss.backward()
         self.flat.flat.grad = self.reducer.finish()
@@ -214,7 +215,7 @@ class Trainer:
         for p in self.flat.params:
             p.grad = None
         self.reducer.reset()
-        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"], **_n_cntxt_of(batch))
+        out = self.model(batch["X_cntxt"], batch["Y_cntxt"], batch["X_trgt"], batch["Y_trgt"], **_counts_of(batch))
         loss = self.criterion(out, batch["Y_trgt"])
         timed = self.phase_events is not None and loss.is_cuda
         if timed:
