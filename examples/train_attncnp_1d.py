@@ -3,7 +3,7 @@
 random context / target split on the device, AttnCNP with transformer attention (what the
 reference's notebooks and shipped checkpoints use), Adam, checkpoint in skorch's layout.
 
-    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged]
+    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged] [--predict]
 
 Only the import line differs from a script written against the reference:
     from npf import AttnCNP, CNPFLoss                      # reference
@@ -47,6 +47,9 @@ def main():
                     help="waveforms of different lengths: every task has its own number of samples (between a quarter of --points "
                          "and --points), the data set comes padded with the lengths as n_points, the batch carries n_cntxt and "
                          "n_trgt, and ONE captured graph serves every mix (implies --per-task-contexts)")
+    ap.add_argument("--predict", action="store_true",
+                    help="after training: condition the model on 16 points of one new function and print the predicted mean and "
+                         "95 %% band on a refined grid (model.predict)")
     ap.add_argument("--out", default="/tmp/npf_example_ckpt")
     args = ap.parse_args()
     dev = "cuda:0"
@@ -81,6 +84,17 @@ def main():
                   f"{(step + 1) * args.tasks * args.points / (time.perf_counter() - t0):,.0f} target-points/s")
     trainer.save_checkpoint(args.out, history=[{"steps": args.steps, "loss": float(loss)}])
     print("checkpoint:", sorted(os.listdir(args.out)))
+    if args.predict:
+        if args.dtype == "fp32":
+            model.eval()
+        X, Y = functions(1, args.points, dev, seed=10 ** 7)
+        ctx = torch.linspace(0, args.points - 1, 16, device=dev).long()
+        grid = torch.linspace(-1, 1, 4 * args.points, device=dev).view(1, -1, 1)  # (finer than anything the model was trained on)
+        pred = model.predict(X[:, ctx], Y[:, ctx], grid)  # Prediction(mean, std, quantiles [3, 1, T, 2], probs)
+        print("   x      mean(y0)  2.5 %    97.5 %   mean(y1)  2.5 %    97.5 %")
+        for t in range(0, grid.shape[1], grid.shape[1] // 16):
+            row = [grid[0, t, 0]] + [v for d in (0, 1) for v in (pred.mean[0, t, d], pred.quantiles[0, 0, t, d], pred.quantiles[2, 0, t, d])]
+            print("  ".join(f"{float(v):7.3f}" for v in row))
 
 
 if __name__ == "__main__":

@@ -18,6 +18,7 @@
  *                        sum_log_prob                     npf/losses.py:18-24
  *   npf_gauss_head_bwd   autograd of the above
  *   npf_masked_gauss_head_fwd/bwd  the same over a batch of padded targets whose per-task sizes are device data
+ *   npf_mixture_summary  mean / std / quantiles of the predictive mixture over the latent samples (inference; no reference counterpart)
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -238,6 +239,21 @@ int npf_masked_gauss_head_fwd(const float *suff, const int32_t *n_valid, int32_t
 int npf_masked_gauss_head_bwd(const float *suff, const float *loc, const float *scale, const int32_t *n_valid, int32_t n_tasks,
                               int32_t n_rows, int32_t pts, int32_t dy, int32_t homoskedastic, const float *Y, int32_t n_y_rows,
                               const float *d_loc, const float *d_scale, const float *d_sum_logp, float *d_suff, void *stream);
+
+/* Predictive summary (no reference counterpart: the reference leaves it to the caller's torch code).  Per task b, point t and output
+ * dimension d the predictive distribution is the equal-weight mixture of the n_z Gaussians N(mu_k, sg_k^2) of the rows k * n_tasks + b
+ * of suff ([n_z * n_tasks][pts][2 dy], what the decoder stores), mu / sg by the head's formulas above (homoskedastic: sg_k pooled over
+ * the row's points).  One launch writes mean = 1/n_z sum_k mu_k, std = sqrt(1/n_z sum_k (sg_k^2 + (mu_k - mean)^2)) ([n_tasks][pts][dy]
+ * each) and, with n_probs > 0, quant[n_probs][n_tasks][pts][dy]: quant[j] = x with 1/n_z sum_k Phi((x - mu_k) / sg_k) = probs[j],
+ * solved by Newton steps safeguarded by bisection inside the bracket [min_k, max_k] of mu_k + sg_k z_p[j].  z_p[j] is the standard-
+ * normal quantile of probs[j] (both DEVICE float [n_probs], computed by the caller).  Nothing of size [n_z][n_tasks][pts][dy] is
+ * written.  1 <= n_z <= 128, dy <= 16, n_tasks <= 65535.  n_valid: NULL or a DEVICE int32 [n_tasks] tensor (clamped to [0, pts]):
+ * task b owns its first n_valid[b] points, the pooling covers those, suff beyond is never read and the rows beyond get mean = 0,
+ * std = 1, quant[j] = z_p[j] (loc = 0, scale = 1 of npf_masked_gauss_head_fwd); full counts equal the NULL launch bit for bit.
+ * n_probs == 0: z_p, probs and quant may be NULL. */
+int npf_mixture_summary(const float *suff, const int32_t *n_valid, int32_t n_z, int32_t n_tasks, int32_t pts, int32_t dy,
+                        int32_t homoskedastic, const float *z_p, int32_t n_probs, const float *probs, float *mean, float *std,
+                        float *quant, void *stream);
 
 /* ---- Monte-Carlo objectives over the latent samples (npf/losses.py:126-276) ------------ */
 /* log_w: row-major [n_z][n_tasks], the log weight of latent sample k for task b: sum_t log p(y_t | z_k), plus

@@ -10,19 +10,6 @@ namespace npf {
 
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();  // red may still be read by a previous call
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
-  return s;
-}
-
-__device__ __forceinline__ float softplus_t(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float softplus_grad(float x) { return x > 20.f ? 1.f : 1.f / (1.f + expf(-x)); }
 
 __global__ __launch_bounds__(256) void gauss_head_fwd_kernel(const float* __restrict__ suff, int pts, int dy, int homosk,

@@ -23,4 +23,20 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
     if (e__ != hipSuccess) return NPF_ELAUNCH; \
   } while (0)
 
+// Sum over the threads of a workgroup (whole wavefronts, <= 8 of them); ``red``: 8 floats of LDS.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();  // red may still be read by a previous call
+  if ((threadIdx.x & 63) == 0) red[wave] = v;
+  __syncthreads();
+  float s = 0.f;
+  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
+  return s;
+}
+
+// softplus of the Gaussian head's scale: scale = 0.01 + 0.99 softplus(raw) (npf/neuralproc/base.py:116)
+__device__ __forceinline__ float softplus_t(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+
 }  // namespace npf

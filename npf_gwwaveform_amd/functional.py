@@ -207,6 +207,71 @@ def gauss_head(suff: torch.Tensor, Y: Optional[torch.Tensor], dy: int, homoskeda
     return _GaussHeadFn.apply(suff, Y, dy, homoskedastic, want_dist)
 
 
+# ---- predictive summary over the latent samples -------------------------------------------
+MIXTURE_MAX_NZ = 128  # latent samples npf_mixture_summary covers
+_Z_P_CACHE = {}       # (probs, device) -> (z_p, probs) device float32 tensors
+
+
+def check_probs(probs) -> tuple:
+    """``probs`` as a tuple of host floats strictly inside (0, 1); anything else -- a tensor, a scalar, 0, 1 -- is a ValueError."""
+    if isinstance(probs, torch.Tensor) or not isinstance(probs, (tuple, list)):
+        raise ValueError(f"probs must be a host sequence (tuple / list) of probabilities, got {type(probs).__name__}")
+    out = []
+    for p in probs:
+        if isinstance(p, torch.Tensor) or isinstance(p, bool) or not isinstance(p, (int, float)):
+            raise ValueError(f"probs must hold host floats, got {type(p).__name__}")
+        if not (0.0 < float(p) < 1.0):
+            raise ValueError(f"probs must lie strictly inside (0, 1), got {p}")
+        out.append(float(p))
+    return tuple(out)
+
+
+def normal_quantiles(probs) -> tuple:
+    """The standard-normal quantiles of ``probs`` as host floats, computed in float64 (``torch.special.ndtri`` on the CPU)."""
+    probs = check_probs(probs)
+    if not probs:
+        return ()
+    return tuple(torch.special.ndtri(torch.tensor(probs, dtype=torch.float64)).tolist())
+
+
+def _z_p_device(probs: tuple, device: torch.device):
+    """(z_p, probs) as device float32 tensors, uploaded once per (probs, device): a captured replay uploads nothing."""
+    key = (probs, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    hit = _Z_P_CACHE.get(key)
+    if hit is None:
+        hit = (torch.tensor(normal_quantiles(probs), dtype=torch.float64).to(torch.float32).to(device),
+               torch.tensor(probs, dtype=torch.float64).to(torch.float32).to(device))
+        _Z_P_CACHE[key] = hit
+    return hit
+
+
+def mixture_summary(suff: torch.Tensor, n_z: int, dy: int, homoskedastic: bool, probs=(), n_valid: Optional[torch.Tensor] = None):
+    """(mean, std, quantiles) of the equal-weight mixture over the latent samples of the Gaussians the head makes of the raw decoder
+    output ``suff`` [n_z * B, pts, 2 * dy] (row ``k * B + b``): ``mean`` / ``std`` [B, pts, dy], ``quantiles`` [len(probs), B, pts, dy].
+    One ``npf_mixture_summary`` launch, inference only (no autograd); nothing of size [n_z, B, pts, dy] is written.  ``probs``: a host
+    sequence of probabilities strictly inside (0, 1).  ``n_valid``: device integer tensor [B], the real points of every task of a
+    padded batch (rows beyond: mean 0, std 1, the standard-normal quantiles)."""
+    probs = check_probs(probs)
+    if not suff.is_cuda or suff.dtype != torch.float32:
+        raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    n_rows, pts, two_dy = suff.shape
+    if two_dy != 2 * dy or n_z < 1 or n_rows % n_z != 0:
+        raise ValueError(f"suff of shape {tuple(suff.shape)} does not hold n_z={n_z} samples of a {dy}-dimensional head")
+    if n_z > MIXTURE_MAX_NZ:
+        raise NotImplementedError(f"mixture_summary covers up to {MIXTURE_MAX_NZ} latent samples (got {n_z})")
+    B = n_rows // n_z
+    suff = suff.detach().contiguous()
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    mean = torch.empty((B, pts, dy), dtype=torch.float32, device=suff.device)
+    std = torch.empty_like(mean)
+    quant = torch.empty((len(probs), B, pts, dy), dtype=torch.float32, device=suff.device)
+    z_p, p_dev = _z_p_device(probs, suff.device) if probs else (None, None)
+    L.check(L.load().npf_mixture_summary(L.ptr(suff), _iptr(nv) if nv is not None else None, n_z, B, pts, dy, int(homoskedastic),
+                                         L.ptr(z_p), len(probs), L.ptr(p_dev), L.ptr(mean), L.ptr(std),
+                                         L.ptr(quant) if probs else None, L.stream_ptr()), "npf_mixture_summary")
+    return mean, std, quant
+
+
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------
 MC_MEAN, MC_LOGMEANEXP, MC_SUMO = 0, 1, 2
 

@@ -19,7 +19,7 @@ from __future__ import annotations
 import abc
 import math
 from functools import partial
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, MergeFlatInputs, MultiheadAttender
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution"]
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction"]
 
 
 def MultivariateNormalDiag(loc, scale_diag):
@@ -39,6 +39,15 @@ def MultivariateNormalDiag(loc, scale_diag):
     if loc.dim() < 1:
         raise ValueError("loc must be at least one-dimensional.")
     return Independent(Normal(loc, scale_diag, validate_args=False), 1)
+
+
+class Prediction(NamedTuple):
+    """Summary of the predictive distribution p(y | context) at the queried points (:meth:`HeadDistribution.summary`): for a
+    latent model the equal-weight mixture over the latent samples of the Gaussians the head makes, else that one Gaussian."""
+    mean: torch.Tensor       # [B, T, y_dim]
+    std: torch.Tensor        # [B, T, y_dim]
+    quantiles: torch.Tensor  # [len(probs), B, T, y_dim]
+    probs: Tuple[float, ...]
 
 
 class HeadDistribution(Independent):
@@ -75,6 +84,49 @@ class HeadDistribution(Independent):
                                       n_valid=self._n_trgt)
             self._slp = (Y_trgt, slp.view(n_z, B))
         return self._slp[1]
+
+    def summary(self, probs=(0.025, 0.5, 0.975)) -> Prediction:
+        """Mean, standard deviation and the ``probs``-quantiles of the predictive distribution per target point and output
+        dimension, marginal over the latent samples (the equal-weight mixture of the ``n_z`` Gaussians): one
+        ``npf_mixture_summary`` launch on the raw decoder output.  ``loc`` / ``scale`` are not materialised (``base_dist`` is left
+        alone) and nothing of size [n_z, B, T, y_dim] is written.  Inference only: no gradient flows through the result.  ``probs``:
+        a host sequence of probabilities strictly inside (0, 1); padded rows (``n_trgt``) get mean 0, std 1 and the standard-normal
+        quantiles."""
+        probs = FN.check_probs(probs)
+        n_z = self.batch_shape[0]
+        mean, std, quant = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, probs=probs, n_valid=self._n_trgt)
+        return Prediction(mean, std, quant, probs)
+
+
+class Conditioned:
+    """A model conditioned on one context set (:meth:`NeuralProcessFamily.condition`): the encoded context points, their
+    representation, and for a latent model q(z | C) with one draw of latent samples.  :meth:`query` evaluates the predictive
+    distribution on any target grid from that state -- the context side is not run again and every query belongs to the same
+    sampled functions ``z_samples``.  The model's parameters are read at query time: condition again after changing them."""
+
+    def __init__(self, model, Xc_pt, R, z_samples, q_zCc, n_cntxt, B, C, fused_t):
+        self._model, self._Xc_pt, self._R = model, Xc_pt, R
+        self.z_samples, self.q_zCc = z_samples, q_zCc  # [n_z, B, 1, z_dim] and q(z | C); None for CNP / AttnCNP
+        self.n_cntxt, self.B, self.C = n_cntxt, B, C
+        self._fused_t = fused_t  # (decided at conditioning time: the context tensors were stored for that target side)
+
+    def query(self, X_trgt, n_trgt=None) -> HeadDistribution:
+        """p(y | context, z) at ``X_trgt`` [B, T, x_dim] -> :class:`HeadDistribution` with batch shape [n_z, B, T]: the launches
+        ``forward`` runs for its target side at these sizes (the masked route if the context was conditioned with ``n_cntxt``),
+        with the stored latent samples.  ``n_trgt``: per-task target sizes of a padded grid, as in ``forward``.  Inference only
+        (``torch.no_grad`` semantics), no host sync: a query and its ``summary`` can be captured in one graph."""
+        m = self._model
+        with torch.no_grad():
+            if n_trgt is not None:
+                n_trgt = m._check_n_trgt(n_trgt, X_trgt)
+            m._check_tensors(X_trgt)
+            if X_trgt.dim() != 3 or X_trgt.shape[0] != self.B:
+                raise ValueError(f"X_trgt must be [B={self.B}, T, x_dim] (the batch the model was conditioned on), got {list(X_trgt.shape)}")
+            if X_trgt.shape[1] == 0:
+                raise ValueError("no target points")
+            latent = (self.z_samples, self.q_zCc) if self.z_samples is not None else None
+            return m._target_stage(self._Xc_pt, self._R, X_trgt, None, self.B, self.C, self.n_cntxt, n_trgt, self._fused_t,
+                                   latent=latent)[0]
 
 
 def _q_z_scale(z_scale):
@@ -162,11 +214,28 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         T = X_trgt.shape[1]
         if T == 0:
             raise ValueError("no target points")
-        if n_cntxt is not None and C > 0:
-            return self._forward_padded(X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt, n_trgt)
+        fused_t = self._fused_target_side(C, T)
+        Xc_pt, R = self._context_stage(X_cntxt, Y_cntxt, n_cntxt, fused_t)
+        return self._target_stage(Xc_pt, R, X_trgt, Y_trgt, B, C, n_cntxt, n_trgt, fused_t)
+
+    def _context_stage(self, X_cntxt, Y_cntxt, n_cntxt, fused_t):
+        """Everything ``forward`` runs before it touches the targets -> (encoded context points ``Xc_pt``, representation ``R``).
+        ``n_cntxt`` (device int32 [B], with C > 0): the padded route -- the per-point stages -- x-encoder, XY-encoder, over all rows
+        of the padded context -- keep the launches of an unfused step; what ties the points of a task together (the mean over the
+        context here, the attention in ``_target_stage``) runs on the masked kernels (csrc/masked_kernels.hip).  ``fused_t``: will
+        the target side be one x6 program (``_fused_target_side``; it decides which companion copies of keys / values the chain
+        launches store)."""
         from . import chain as _chain
 
-        fused_t = self._fused_target_side(C, T)
+        B, C, _ = X_cntxt.shape
+        if n_cntxt is not None and C > 0:
+            if self._fused_context_side(C):
+                from . import x6
+
+                Xc_pt, R_pts = x6.context_side(self, X_cntxt, Y_cntxt)
+                return Xc_pt, self._pool_pt(R_pts, B, n_valid=n_cntxt)
+            Xc_pt = self._xenc_pt(X_cntxt)
+            return Xc_pt, self._encode_globally_pt(Xc_pt, Y_cntxt, B, C, n_valid=n_cntxt)
         fused_c = self._fused_context_side(C)
         if fused_c and self._attentive and not fused_t and _chain.COMPUTE_DTYPE == "bf16":
             fused_c = False  # (the bf16 attention chain streams the bf16 images of keys / values its producer chains store)
@@ -175,12 +244,24 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
             from . import x6
 
             Xc_pt, R_pts = x6.context_side(self, X_cntxt, Y_cntxt)
-            R = self._pool_pt(R_pts, B)
-        else:
-            Xc_pt = self._xenc_pt(X_cntxt, with_tr=self._attentive and not fused_t) if C > 0 else None
-            R = self._encode_globally_pt(Xc_pt, Y_cntxt, B, C)
-        if fused_t:
-            Xt_pt, self._X_trgt_raw = None, X_trgt  # (the target side runs as one x6 program from the raw features)
+            return Xc_pt, self._pool_pt(R_pts, B)
+        Xc_pt = self._xenc_pt(X_cntxt, with_tr=self._attentive and not fused_t) if C > 0 else None
+        return Xc_pt, self._encode_globally_pt(Xc_pt, Y_cntxt, B, C)
+
+    def _target_stage(self, Xc_pt, R, X_trgt, Y_trgt, B, C, n_cntxt, n_trgt, fused_t, latent=None):
+        """The rest of ``forward`` from what ``_context_stage`` returned -> ``(p_yCc, z_samples, q_zCc, q_zCct)``.  ``latent``:
+        ``(z_samples, q_zCc)`` drawn earlier (a conditioned model, :meth:`condition`) instead of the latent path here.  On the padded
+        route (``n_cntxt`` with C > 0) the fused target side (x6.target_side) is not taken: its softmax has the key count as a launch
+        argument.  With ``n_trgt`` the masked attention then skips the queries beyond the count, and on either route the head / the
+        target-side mean of the latent path read it."""
+        T = X_trgt.shape[1]
+        padded = n_cntxt is not None and C > 0
+        n_valid = n_cntxt if padded else None
+        X_raw = None
+        if padded:
+            Xt_pt = self._xenc_pt(X_trgt)
+        elif fused_t:
+            Xt_pt, X_raw = None, X_trgt  # (the target side runs as one x6 program from the raw features)
         elif self._xenc_with_query_projection(C, T):
             # multihead / transformer attention with 16-wide heads: the target x-encoder and the attender's query projection as
             # one x6 program (x6.xenc_proj)
@@ -190,15 +271,57 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
             Xt_pt.proj = q_proj
         else:
             Xt_pt = self._xenc_pt(X_trgt)
-        if self.encoded_path in ["latent", "both"]:
-            z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T, n_trgt=n_trgt)
-        else:
-            z_samples, q_zCc, q_zCct = None, None, None
-        if self.encoded_path == "latent":
-            R = None
-        suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T)  # [n_z * B, T, 2 dy]
-        p_yCc = self._head(suff, Y_trgt, B, T, n_trgt=n_trgt)
-        return p_yCc, z_samples, q_zCc, q_zCct
+        self._X_trgt_raw = X_raw  # (per-call: read by the two methods below only)
+        try:
+            if latent is not None:
+                z_samples, q_zCc, q_zCct = latent[0], latent[1], None
+            elif self.encoded_path in ["latent", "both"]:
+                z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T, n_valid=n_valid, n_trgt=n_trgt)
+            else:
+                z_samples, q_zCc, q_zCct = None, None, None
+            if self.encoded_path == "latent":
+                R = None
+            if padded:
+                suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=n_valid, n_q_valid=n_trgt)
+            else:
+                suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T)  # [n_z * B, T, 2 dy]
+        finally:
+            self._X_trgt_raw = None
+        return self._head(suff, Y_trgt, B, T, n_trgt=n_trgt), z_samples, q_zCc, q_zCct
+
+    # ------------------------------------------------------------------ conditioned prediction
+    def _n_z_for(self, n_z_samples=None) -> Optional[int]:
+        """Latent samples of an inference call (None: not a latent model)."""
+        return None
+
+    def condition(self, X_cntxt, Y_cntxt, n_cntxt=None, n_z_samples=None) -> "Conditioned":
+        """Encode the context once: everything ``forward`` runs before it first touches the targets, on the kernels ``forward`` would
+        take for this context size (``n_cntxt``: the padded route, as in ``forward``), and for a latent model q(z | C) and ONE draw
+        of ``n_z_samples`` latent samples (default: ``n_z_samples_test`` / ``n_z_samples_train`` by the model's mode).  The returned
+        :class:`Conditioned` answers any number of :meth:`Conditioned.query` calls from that state: every grid queried belongs to
+        the same sampled functions.  Inference only (``torch.no_grad`` semantics, the model's train / eval mode respected); no host
+        sync, so the training-time [-1, 1] range check is not applied."""
+        with torch.no_grad():
+            n_z = self._n_z_for(n_z_samples)
+            if n_cntxt is not None:
+                n_cntxt = self._check_n_cntxt(n_cntxt, X_cntxt)
+            self._check_tensors(X_cntxt, Y_cntxt)
+            B, C, _ = X_cntxt.shape
+            if n_z is not None:
+                self.n_z_samples = n_z  # (read by AttnLNP's dispatch rule; ``query`` uses what is stored below, not this attribute)
+            fused_t = self._fused_target_side(C, 1)  # (the rule does not depend on the number of targets: x6.target_side_usable)
+            Xc_pt, R = self._context_stage(X_cntxt, Y_cntxt, n_cntxt, fused_t)
+            z_samples = q_zCc = None
+            if n_z is not None:
+                q_zCc = self._infer_q_zCc(R, B, n_cntxt if C > 0 else None)
+                z_samples = q_zCc.rsample([n_z])
+        return Conditioned(self, Xc_pt, R, z_samples, q_zCc, n_cntxt, B, C, fused_t)
+
+    def predict(self, X_cntxt, Y_cntxt, X_trgt, n_cntxt=None, n_trgt=None, n_z_samples=None, probs=(0.025, 0.5, 0.975)) -> Prediction:
+        """``condition(X_cntxt, Y_cntxt, n_cntxt, n_z_samples).query(X_trgt, n_trgt).summary(probs)``: mean, standard deviation and
+        quantiles of p(y | context) at ``X_trgt``."""
+        probs = FN.check_probs(probs)
+        return self.condition(X_cntxt, Y_cntxt, n_cntxt=n_cntxt, n_z_samples=n_z_samples).query(X_trgt, n_trgt=n_trgt).summary(probs)
 
     def _check_n_cntxt(self, n_cntxt, X_cntxt):
         """The per-task context sizes as a device int32 [B] tensor; refuses what the padded path does not implement."""
@@ -226,37 +349,9 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
             raise ValueError(f"n_trgt lives on {n.device}, the batch on {X_trgt.device}")
         return n
 
-    def _forward_padded(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt, n_trgt=None):
-        """``forward`` over a padded batch (``n_cntxt``: device int32 [B]; ``n_trgt``: the same for the targets, or None).  The per-point stages -- x-encoder, XY-encoder, over all
-        rows of the padded context -- and the decoder keep the launches of an unfused step; what ties the points of a task together
-        (attention over the context, the mean over it) runs on the masked kernels (csrc/masked_kernels.hip).  The fused target
-        side (x6.target_side) is not taken: its softmax has the key count as a launch argument.  With ``n_trgt`` the masked attention
-        skips the queries beyond the count, and the head / the target-side mean of the latent path read it."""
-        B, C, _ = X_cntxt.shape
-        T = X_trgt.shape[1]
-        if self._fused_context_side(C):
-            from . import x6
-
-            Xc_pt, R_pts = x6.context_side(self, X_cntxt, Y_cntxt)
-            R = self._pool_pt(R_pts, B, n_valid=n_cntxt)
-        else:
-            Xc_pt = self._xenc_pt(X_cntxt)
-            R = self._encode_globally_pt(Xc_pt, Y_cntxt, B, C, n_valid=n_cntxt)
-        Xt_pt = self._xenc_pt(X_trgt)
-        if self.encoded_path in ["latent", "both"]:
-            z_samples, q_zCc, q_zCct = self._latent_path_pt(R, C, Xt_pt, Y_trgt, B, T, n_valid=n_cntxt, n_trgt=n_trgt)
-        else:
-            z_samples, q_zCc, q_zCct = None, None, None
-        if self.encoded_path == "latent":
-            R = None
-        suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=n_cntxt, n_q_valid=n_trgt)
-        return self._head(suff, Y_trgt, B, T, n_trgt=n_trgt), z_samples, q_zCc, q_zCct
-
     def _validate_inputs(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt):
         """base.py:241-247: features must be in [-1, 1] during training (the padding rows of a padded batch included)."""
-        for t in (X_cntxt, Y_cntxt, X_trgt, Y_trgt):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32):
-                raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+        self._check_tensors(X_cntxt, Y_cntxt, X_trgt, Y_trgt)
         if self.training and self.validate_inputs:
             # one device reduction and ONE host sync per step (every sync drains the stream and
             # costs a launch bubble); NaNs fail the test like the reference's (x>=-1)&(x<=1)
@@ -274,6 +369,12 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
                 lo = min(X_cntxt.min().item() if X_cntxt.numel() else 0.0, X_trgt.min().item())
                 hi = max(X_cntxt.max().item() if X_cntxt.numel() else 0.0, X_trgt.max().item())
                 raise ValueError(f"Features during training should be in [-1,1]. Got [{lo}, {hi}].")
+
+    @staticmethod
+    def _check_tensors(*tensors):
+        for t in tensors:
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+                raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
 
     def check_deferred_inputs(self):
         """``validate_inputs == "deferred"``: raise the reference's ValueError (base.py:244-247) if any training batch
@@ -385,11 +486,18 @@ class LatentNeuralProcessFamily(NeuralProcessFamily):
         return d
 
     def forward(self, *args, **kwargs):
-        try:  # scipy random variable = random number of samples (base.py:478-486)
-            self.n_z_samples = self.n_z_samples_train.rvs() if self.training else self.n_z_samples_test.rvs()
-        except AttributeError:
-            self.n_z_samples = self.n_z_samples_train if self.training else self.n_z_samples_test
+        self.n_z_samples = self._n_z_for()
         return super().forward(*args, **kwargs)
+
+    def _n_z_for(self, n_z_samples=None) -> int:
+        if n_z_samples is not None:
+            if int(n_z_samples) < 1:
+                raise ValueError(f"n_z_samples must be at least 1, got {n_z_samples}")
+            return int(n_z_samples)
+        try:  # scipy random variable = random number of samples (base.py:478-486)
+            return self.n_z_samples_train.rvs() if self.training else self.n_z_samples_test.rvs()
+        except AttributeError:
+            return self.n_z_samples_train if self.training else self.n_z_samples_test
 
     def infer_latent_dist(self, X, R):
         """base.py:516-547 on row-major R."""
@@ -415,10 +523,14 @@ class LatentNeuralProcessFamily(NeuralProcessFamily):
             q_zCct, sampling_dist = None, q_zCc
         return sampling_dist.rsample([self.n_z_samples]), q_zCc, q_zCct
 
+    def _infer_q_zCc(self, R, B, n_valid=None):
+        """q(z | C) from the context representation (``n_valid``: the context sizes of a padded batch)."""
+        return self._latent_dist_from(self._lat_input(R, B) if n_valid is None else self._lat_input(R, B, n_valid=n_valid))
+
     def _latent_path_pt(self, R, C, Xt_pt, Y_trgt, B, T, n_valid=None, n_trgt=None):
         # (n_valid: the context sizes of a padded batch; n_trgt: the target sizes -- the target-side encode below pools over the
         # first n_trgt[b] targets, zeros for a task without any, as encode_globally at zero points)
-        q_zCc = self._latent_dist_from(self._lat_input(R, B) if n_valid is None else self._lat_input(R, B, n_valid=n_valid))
+        q_zCc = self._infer_q_zCc(R, B, n_valid)
         if self.is_q_zCct and Y_trgt is not None:
             if Xt_pt is None:
                 # (forward left the target side to one x6 program, which encodes the targets itself: the target-side latent
