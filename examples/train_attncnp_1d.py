@@ -3,7 +3,7 @@
 random context / target split on the device, AttnCNP with transformer attention (what the
 reference's notebooks and shipped checkpoints use), Adam, checkpoint in skorch's layout.
 
-    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged] [--predict]
+    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged] [--predict] [--rollout]
 
 Only the import line differs from a script written against the reference:
     from npf import AttnCNP, CNPFLoss                      # reference
@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--predict", action="store_true",
                     help="after training: condition the model on 16 points of one new function and print the predicted mean and "
                          "95 %% band on a refined grid (model.predict)")
+    ap.add_argument("--rollout", action="store_true",
+                    help="after training (fp32): condition on 16 points of one new function with room to grow and draw ONE "
+                         "autoregressive sample on a 32-point grid (Conditioned.rollout: query, draw, feed the draw back)")
     ap.add_argument("--out", default="/tmp/npf_example_ckpt")
     args = ap.parse_args()
     dev = "cuda:0"
@@ -95,6 +98,16 @@ def main():
         for t in range(0, grid.shape[1], grid.shape[1] // 16):
             row = [grid[0, t, 0]] + [v for d in (0, 1) for v in (pred.mean[0, t, d], pred.quantiles[0, 0, t, d], pred.quantiles[2, 0, t, d])]
             print("  ".join(f"{float(v):7.3f}" for v in row))
+    if args.rollout and args.dtype == "fp32":  # (a growing context runs the masked route: fp32 only)
+        model.eval()
+        X, Y = functions(1, args.points, dev, seed=10 ** 7)
+        ctx = torch.linspace(0, args.points - 1, 16, device=dev).long()
+        grid = torch.linspace(-1, 1, 32, device=dev).view(1, -1, 1)
+        post = model.condition_with_capacity(X[:, ctx], Y[:, ctx], capacity=16 + 32)
+        sample = post.rollout(grid)  # [1, 32, 2]; ``post`` is now conditioned on the 16 points and the 32 draws
+        print("autoregressive sample   x      y0       y1")
+        for t in range(0, 32, 4):
+            print(f"                     {float(grid[0, t, 0]):7.3f}  {float(sample[0, t, 0]):7.3f}  {float(sample[0, t, 1]):7.3f}")
 
 
 if __name__ == "__main__":

@@ -29,6 +29,7 @@
  *   npf_gather_points    CntxtTrgtGetter.select              npf/utils/datasplit.py:246-255
  *   npf_masked_attn_fwd/bwd (and _fwd_nq / _bwd_nq: padded queries too), npf_masked_mean_fwd/bwd  DotAttender.forward / torch.mean(R_cntxt, dim=1) of a padded batch
  *                        whose per-task context sizes are device data (no reference counterpart: the reference cuts the batch)
+ *   npf_append_points    new context rows behind the rows each task of such a padded batch holds (no reference counterpart)
  *   npf_split_heads/npf_merge_heads  MultiheadAttender._make_multiheaded / _concatenate_multiheads
  *                                                         npf/architectures/attention.py:505-527
  *
@@ -529,6 +530,25 @@ int npf_masked_mean_fwd(const float *R_pt, const int32_t *n_valid, int32_t n_tas
 /* dR_pt[task][p][f] (+)= d_out[task][f] / n_valid[task] for p < n_valid[task], 0 beyond (accumulate as npf_mean_agg_bwd). */
 int npf_masked_mean_bwd(const float *d_out, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *dR_pt,
                         int32_t accumulate, void *stream);
+
+/* ---- growing contexts: rows appended at per-task offsets that are device data (csrc/append_kernels.hip) ----------------------
+ * For every pair i < n_pairs (<= NPF_APPEND_MAX_PAIRS), task b and j < clamp(n_new[b], 0, n_rows) (n_new == NULL: j < n_rows):
+ *   dst_i(b, clamp(n_valid[b], 0, capacity) + j, :) = src_i(b, j, :)    over all F_i features,
+ * src_i: PT32 [n_tasks][n_rows][F_i], dst_i: PT32 [n_tasks][capacity][F_i], F_i % 32 == 0.  Rows that would land at or beyond
+ * `capacity` are dropped; no other row of dst_i (and nothing outside its `capacity` rows' tiles) is written.  Then, in a second
+ * launch in stream order -- after every row of every pair has been placed -- n_valid[b] <- min(n_valid[b] + n_new[b], capacity)
+ * (both clamped as above) in place.  n_valid / n_new: DEVICE int32 [n_tasks] tensors the kernels read, the host never does: the
+ * call sits in a captured graph and sees new counts at every replay.  `pairs` is read on the host at call time.  n_tasks <= 65535.
+ * No reference counterpart (the reference re-encodes the whole context). */
+#define NPF_APPEND_MAX_PAIRS 3
+typedef struct npf_append_pair {
+  const float *src;
+  float *dst;
+  int32_t F;
+  int32_t reserved;
+} npf_append_pair_t;
+int npf_append_points(const npf_append_pair_t *pairs, int32_t n_pairs, int32_t *n_valid, const int32_t *n_new, int32_t n_tasks,
+                      int32_t n_rows, int32_t capacity, void *stream);
 
 int npf_version(void);
 

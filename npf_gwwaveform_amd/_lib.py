@@ -87,6 +87,14 @@ class NpfX6Op(C.Structure):
                 ("softmax_n", C.c_int32), ("softmax_scale", C.c_float), ("sbwd_scale", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
+NPF_APPEND_MAX_PAIRS = 3
+
+
+class NpfAppendPair(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("F", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(NpfAppendPair) == 24
 assert C.sizeof(NpfX6Op) == 17 * 8 + 8 * 4
 assert C.sizeof(NpfOp) == 80 and C.sizeof(NpfProgram) == 32 + 80 * NPF_MAX_OPS and C.sizeof(NpfWgradJob) == 72 and C.sizeof(NpfWprepJob) == 32
 
@@ -130,6 +138,7 @@ SIGNATURES = {
     "npf_mixture_summary": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "npf_masked_mean_fwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "npf_masked_mean_bwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _i32, _p]),
+    "npf_append_points": (C.c_int, [C.POINTER(NpfAppendPair), _i32, _p, _p, _i32, _i32, _i32, _p]),
     "npf_version": (C.c_int, []),
 }
 

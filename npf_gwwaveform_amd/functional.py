@@ -9,7 +9,7 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from .chain import pad32, pt_empty, tiles_of
+from .chain import pad32, pt_empty, pt_shape, tiles_of
 
 
 # ---- layout ---------------------------------------------------------------------------
@@ -599,3 +599,35 @@ def masked_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: in
     """Mean over the first ``n_valid[task]`` points of a PT32 tensor -> row-major [n_tasks, pad32(F)] (zeros where a task has none):
     ``torch.mean(R, dim=1)`` (npf/neuralproc/np.py:95, attnnp.py:181) of the batch cut per task; counts as in :func:`masked_attention`."""
     return _MaskedMeanFn.apply(R_pt, counts_i32(n_valid, n_tasks), n_tasks, pts, F)
+
+
+# ---- growing contexts: rows appended at per-task offsets that are device data (csrc/append_kernels.hip) ----------------------
+def append_points(pairs, n_valid: torch.Tensor, n_new: Optional[torch.Tensor], n_tasks: int, n_rows: int, capacity: int) -> None:
+    """Append ``n_rows`` new rows per task to padded PT32 tensors, in place (``npf_append_points``: one launch for the rows of all
+    pairs, one behind it for the counts).  ``pairs``: up to three ``(src, dst, F)`` with ``src`` PT32 [n_tasks, n_rows, F] and ``dst``
+    PT32 [n_tasks, capacity, F]; row ``j < clamp(n_new[b], 0, n_rows)`` of ``src`` (``n_new`` None: every row) becomes row
+    ``n_valid[b] + j`` of ``dst``, rows that would land at or beyond ``capacity`` are dropped, no other row is written, and then
+    ``n_valid[b] <- min(n_valid[b] + n_new[b], capacity)``.  ``n_valid`` (updated in place) / ``n_new``: contiguous device int32
+    [n_tasks] tensors, read by the kernels only.  No host read, no allocation, no autograd: the call can sit in a captured graph."""
+    pairs = list(pairs)
+    if not 1 <= len(pairs) <= L.NPF_APPEND_MAX_PAIRS:
+        raise ValueError(f"append_points takes 1 to {L.NPF_APPEND_MAX_PAIRS} (src, dst, F) pairs, got {len(pairs)}")
+    if n_rows < 0 or capacity < 1:
+        raise ValueError(f"append_points needs n_rows >= 0 and capacity >= 1, got {n_rows} and {capacity}")
+    for what, t in (("n_valid", n_valid), ("n_new", n_new)):
+        if t is None and what == "n_new":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (n_tasks,) or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous int32 tensor of shape [{n_tasks}]")
+        if not t.is_cuda:
+            raise ValueError(f"{what} must live on the device (its values are read by the kernels, never by the host)")
+    arr = (L.NpfAppendPair * len(pairs))()
+    for i, (src, dst, F) in enumerate(pairs):
+        if tuple(src.shape) != pt_shape(n_tasks, n_rows, F) or tuple(dst.shape) != pt_shape(n_tasks, capacity, F):
+            raise ValueError(f"pair {i}: expected PT32 tensors of shapes {pt_shape(n_tasks, n_rows, F)} -> {pt_shape(n_tasks, capacity, F)}, "
+                             f"got {tuple(src.shape)} -> {tuple(dst.shape)}")
+        if src.device != n_valid.device or dst.device != n_valid.device:
+            raise ValueError(f"pair {i} and the counts live on different devices")
+        arr[i].src, arr[i].dst, arr[i].F = L.ptr(src), L.ptr(dst), pad32(F)
+    L.check(L.load().npf_append_points(arr, len(pairs), _iptr(n_valid), _iptr(n_new) if n_new is not None else None, n_tasks, n_rows,
+                                       capacity, L.stream_ptr()), "npf_append_points")

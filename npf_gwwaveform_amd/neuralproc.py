@@ -104,11 +104,16 @@ class Conditioned:
     distribution on any target grid from that state -- the context side is not run again and every query belongs to the same
     sampled functions ``z_samples``.  The model's parameters are read at query time: condition again after changing them."""
 
-    def __init__(self, model, Xc_pt, R, z_samples, q_zCc, n_cntxt, B, C, fused_t):
+    def __init__(self, model, Xc_pt, R, z_samples, q_zCc, n_cntxt, B, C, fused_t, capacity=None, R_pts=None, eps=None):
         self._model, self._Xc_pt, self._R = model, Xc_pt, R
         self.z_samples, self.q_zCc = z_samples, q_zCc  # [n_z, B, 1, z_dim] and q(z | C); None for CNP / AttnCNP
         self.n_cntxt, self.B, self.C = n_cntxt, B, C
         self._fused_t = fused_t  # (decided at conditioning time: the context tensors were stored for that target side)
+        # a growing context (``condition_with_capacity``): the state is stored at ``capacity`` rows per task, ``n_cntxt`` holds the live
+        # device counts, ``_R_pts`` the per-point representations the pooled ``_R`` of CNP / LNP is refreshed from, ``eps`` the
+        # standard-normal draw behind ``z_samples``; ``n_rows_bound``: what the host knows of the counts, an upper bound
+        self.capacity, self._R_pts, self.eps = capacity, R_pts, eps
+        self.n_rows_bound = C
 
     def query(self, X_trgt, n_trgt=None) -> HeadDistribution:
         """p(y | context, z) at ``X_trgt`` [B, T, x_dim] -> :class:`HeadDistribution` with batch shape [n_z, B, T]: the launches
@@ -125,8 +130,90 @@ class Conditioned:
             if X_trgt.shape[1] == 0:
                 raise ValueError("no target points")
             latent = (self.z_samples, self.q_zCc) if self.z_samples is not None else None
-            return m._target_stage(self._Xc_pt, self._R, X_trgt, None, self.B, self.C, self.n_cntxt, n_trgt, self._fused_t,
+            n_keys = self.C if self.capacity is None else self.capacity  # (a growing context: always the padded route)
+            return m._target_stage(self._Xc_pt, self._R, X_trgt, None, self.B, n_keys, self.n_cntxt, n_trgt, self._fused_t,
                                    latent=latent)[0]
+
+    def extend(self, X_new, Y_new, n_new=None) -> "Conditioned":
+        """Add observations to the context, in place -> ``self``.  ``X_new`` [B, N, x_dim], ``Y_new`` [B, N, y_dim]; ``n_new`` (integer
+        device tensor [B], optional): task ``b`` adds its first ``n_new[b]`` rows only.  The per-point stages (x-encoder, XY-encoder)
+        run on the ``N`` new points, one ``npf_append_points`` launch places them behind the rows every task holds and advances
+        ``n_cntxt``, and what depends on the whole context is refreshed: the pooled representation of CNP / LNP, and for a latent
+        model ``q_zCc`` and ``z_samples = loc + scale * eps`` with the stored ``eps`` (the same sampled functions, given more data).
+        Every state tensor keeps its storage, so a captured ``extend`` followed by ``query`` replays.  Inference only, no host sync:
+        the counts are never read by the host, which only keeps an upper bound of the rows offered (C + the sum of all ``N``, whatever
+        ``n_new`` says) and raises ``ValueError`` when that exceeds ``capacity``."""
+        m = self._model
+        if self.capacity is None:
+            raise ValueError("extend needs a growing context: condition with model.condition_with_capacity(..., capacity=M)")
+        if X_new.dim() != 3 or X_new.shape[0] != self.B or X_new.shape[2] != m.x_dim:
+            raise ValueError(f"X_new must be [B={self.B}, N, x_dim={m.x_dim}], got {list(X_new.shape)}")
+        if Y_new.dim() != 3 or tuple(Y_new.shape[:2]) != tuple(X_new.shape[:2]) or Y_new.shape[2] != m.y_dim:
+            raise ValueError(f"Y_new must be [B={self.B}, N={X_new.shape[1]}, y_dim={m.y_dim}], got {list(Y_new.shape)}")
+        N = X_new.shape[1]
+        if self.n_rows_bound + N > self.capacity:
+            raise ValueError(f"extend: {self.n_rows_bound} rows offered so far + {N} new ones exceed capacity={self.capacity}")
+        if N == 0:
+            return self
+        m._check_tensors(X_new, Y_new)
+        if n_new is not None:
+            n_new = FN.counts_i32(n_new, self.B, "n_new")
+            if n_new.device != X_new.device:
+                raise ValueError(f"n_new lives on {n_new.device}, the batch on {X_new.device}")
+        with torch.no_grad():
+            Xn_pt, Rn_pts = m._encode_points(X_new, Y_new)
+            pairs = [(Rn_pts.t, self._R_pts.t, m.r_dim)]
+            if self._Xc_pt is not None:
+                pairs.append((Xn_pt.t, self._Xc_pt.t, m.x_transf_dim))
+            FN.append_points(pairs, self.n_cntxt, n_new, self.B, N, self.capacity)
+            self.n_rows_bound += N
+            self._refresh()
+        return self
+
+    def _refresh(self):
+        """What depends on the whole context, recomputed from the stored rows and the live counts, in place."""
+        m = self._model
+        if self._R is not self._R_pts:  # (CNP / LNP: the mean over the stored per-point representations)
+            self._R.copy_(m._pool_pt(self._R_pts, self.B, n_valid=self.n_cntxt))
+        if self.eps is not None:
+            q = m._infer_q_zCc(self._R, self.B, self.n_cntxt).base_dist
+            self.q_zCc.base_dist.loc.copy_(q.loc)
+            self.q_zCc.base_dist.scale.copy_(q.scale)
+            self.z_samples.copy_(q.loc + q.scale * self.eps)
+
+    def rollout(self, X_trgt, eps=None, chunk=1) -> torch.Tensor:
+        """One autoregressive sample of the function at ``X_trgt`` [B, T, x_dim] -> ``Y`` [B, T, y_dim]: for each block of ``chunk``
+        targets in order, ``query`` the block, draw ``y = loc + scale * eps_block`` and ``extend`` the context by ``(x_block, y)`` --
+        later targets are predicted given the earlier draws, which gives CNP / AttnCNP (whose one-shot predictive is a product of
+        independent Gaussians) coherent samples.  ``eps`` [B, T, y_dim]: the standard-normal noise (default: one ``torch.randn`` draw).
+        One trajectory per task: a latent model needs ``n_z == 1`` (tile the batch for several).  Needs ``capacity`` >= the rows
+        offered so far + T.  NOTE: the state is left extended by the T drawn points -- a later ``query`` is conditioned on them."""
+        m = self._model
+        if self.capacity is None:
+            raise ValueError("rollout needs a growing context: condition with model.condition_with_capacity(..., capacity=M)")
+        if self.z_samples is not None and self.z_samples.shape[0] != 1:
+            raise ValueError(f"rollout draws one trajectory per task: condition with n_z_samples=1 (got {self.z_samples.shape[0]})")
+        if X_trgt.dim() != 3 or X_trgt.shape[0] != self.B or X_trgt.shape[2] != m.x_dim:
+            raise ValueError(f"X_trgt must be [B={self.B}, T, x_dim={m.x_dim}], got {list(X_trgt.shape)}")
+        T = X_trgt.shape[1]
+        if eps is not None and tuple(eps.shape) != (self.B, T, m.y_dim):
+            raise ValueError(f"eps must be [B={self.B}, T={T}, y_dim={m.y_dim}], got {list(eps.shape)}")
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be at least 1, got {chunk}")
+        if self.n_rows_bound + T > self.capacity:
+            raise ValueError(f"rollout: {self.n_rows_bound} rows offered so far + {T} targets exceed capacity={self.capacity}")
+        m._check_tensors(X_trgt, eps)
+        if eps is None:
+            eps = torch.randn(self.B, T, m.y_dim, device=X_trgt.device)
+        Y = torch.empty(self.B, T, m.y_dim, device=X_trgt.device)
+        for s in range(0, T, chunk):
+            x = X_trgt[:, s:s + chunk].contiguous()
+            p = self.query(x).base_dist
+            y = p.loc[0] + p.scale[0] * eps[:, s:s + chunk]
+            Y[:, s:s + chunk] = y
+            self.extend(x, y)
+        return Y
 
 
 def _q_z_scale(z_scale):
@@ -316,6 +403,63 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
                 q_zCc = self._infer_q_zCc(R, B, n_cntxt if C > 0 else None)
                 z_samples = q_zCc.rsample([n_z])
         return Conditioned(self, Xc_pt, R, z_samples, q_zCc, n_cntxt, B, C, fused_t)
+
+    def condition_with_capacity(self, X_cntxt, Y_cntxt, capacity, n_cntxt=None, n_z_samples=None) -> "Conditioned":
+        """:meth:`condition` into a context that can grow: the state is stored at ``capacity`` >= C rows per task (C = 0 is allowed)
+        together with its own device counts (a copy of ``n_cntxt``, or C for every task), and :meth:`Conditioned.extend` /
+        :meth:`Conditioned.rollout` add observations to it in place.  Such a model always runs the padded route of ``forward``
+        (``n_cntxt``) with ``capacity`` key rows: masked attention / mean stop at the counts and never read the rows beyond.  Stored:
+        the encoded context points (attentive models) and the per-point representations (every model: CNP / LNP re-pool their mean
+        from them).  A latent model draws ``eps = randn([n_z, B, 1, z_dim])`` once -- the draw ``rsample`` makes in ``condition`` -- keeps
+        it (``Conditioned.eps``) and sets ``z_samples = loc + scale * eps``, again after every ``extend``.  Not implemented, as with
+        ``n_cntxt``: ``is_self_attn=True`` and the bf16 compute mode."""
+        from . import chain as _chain
+
+        if getattr(self, "is_self_attn", False):
+            raise NotImplementedError("capacity is not implemented for self-attention context encoders (is_self_attn=True)")
+        if _chain.COMPUTE_DTYPE != "fp32":
+            raise NotImplementedError("capacity is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
+        with torch.no_grad():
+            n_z = self._n_z_for(n_z_samples)
+            if X_cntxt.dim() != 3 or Y_cntxt.dim() != 3 or X_cntxt.shape[:2] != Y_cntxt.shape[:2]:
+                raise ValueError(f"X_cntxt / Y_cntxt must be [B, C, x_dim] / [B, C, y_dim], got {list(X_cntxt.shape)} / {list(Y_cntxt.shape)}")
+            B, C, _ = X_cntxt.shape
+            capacity = int(capacity)
+            if capacity < max(C, 1):
+                raise ValueError(f"capacity={capacity} must be at least the context size C={C} (and at least 1)")
+            self._check_tensors(X_cntxt, Y_cntxt)
+            if n_cntxt is not None:
+                n_cntxt = self._check_n_cntxt(n_cntxt, X_cntxt)
+            if n_z is not None:
+                self.n_z_samples = n_z
+            dev = X_cntxt.device
+            # (zeros: the rows beyond the counts are never read, but they stay finite for whoever looks at the state)
+            R_pts = PTensor(torch.zeros(pt_shape(B, capacity, self.r_dim), device=dev), capacity, self.r_dim)
+            Xc_pt = PTensor(torch.zeros(pt_shape(B, capacity, self.x_transf_dim), device=dev), capacity, self.x_transf_dim) \
+                if self._attentive else None
+            counts = torch.zeros(B, dtype=torch.int32, device=dev)
+            post = Conditioned(self, Xc_pt, R_pts if self._attentive else torch.zeros(B, 1, self.r_dim, device=dev), None, None, counts,
+                               B, C, False, capacity=capacity, R_pts=R_pts)
+            if C > 0:
+                Xn_pt, Rn_pts = self._encode_points(X_cntxt, Y_cntxt)
+                pairs = [(Rn_pts.t, R_pts.t, self.r_dim)] + ([(Xn_pt.t, Xc_pt.t, self.x_transf_dim)] if self._attentive else [])
+                FN.append_points(pairs, counts, n_cntxt, B, C, capacity)
+            post._refresh()
+            if n_z is not None:
+                post.q_zCc = q = self._infer_q_zCc(post._R, B, counts)
+                post.eps = torch.randn(n_z, B, 1, self.z_dim, device=dev)
+                post.z_samples = q.base_dist.loc + q.base_dist.scale * post.eps
+        return post
+
+    def _encode_points(self, X, Y):
+        """The per-point stages of the context side on [B, N, .] points -> (encoded points, per-point representations), PTensors of
+        N rows: the launches the padded route of ``_context_stage`` runs for a context of this size, without its pooling."""
+        if self._fused_context_side(X.shape[1]):
+            from . import x6
+
+            return x6.context_side(self, X, Y)
+        X_pt = self._xenc_pt(X)
+        return X_pt, self._xyenc_pt(X_pt, Y, with_tr=False)
 
     def predict(self, X_cntxt, Y_cntxt, X_trgt, n_cntxt=None, n_trgt=None, n_z_samples=None, probs=(0.025, 0.5, 0.975)) -> Prediction:
         """``condition(X_cntxt, Y_cntxt, n_cntxt, n_z_samples).query(X_trgt, n_trgt).summary(probs)``: mean, standard deviation and
