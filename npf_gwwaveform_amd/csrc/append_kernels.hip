@@ -12,9 +12,6 @@ struct AppendArgs {
   npf_append_pair_t pair[NPF_APPEND_MAX_PAIRS];
 };
 
-// Rows a task holds / adds, clamped to what the tensors hold (the masked kernels clamp their counts the same way).
-__device__ __forceinline__ int ap_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // grid = (source tiles x chunks of 32 feature quads, n_tasks, n_pairs); 256 threads = 8 feature quads x 32 rows, every thread moves up to
 // four 16-byte (row, 4 features) units: 32 consecutive lanes read 512 consecutive bytes of a source tile and write at most two
 // consecutive runs of the destination (the destination rows of one source tile straddle at most one tile boundary).
@@ -26,8 +23,9 @@ __global__ __launch_bounds__(256) void append_rows_kernel(AppendArgs a, const in
   const int tile = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
   const size_t task = blockIdx.y;
   const int p = threadIdx.x & 31, q = threadIdx.x >> 5;
-  const int have = ap_clamp(n_valid[task], M);
-  const int add = n_new ? ap_clamp(n_new[task], N) : N;
+  // rows the task holds / adds, clamped to what the tensors hold
+  const int have = clamp_count(n_valid, task, M);
+  const int add = n_new ? clamp_count(n_new, task, N) : N;
   const int j = tile * 32 + p;       // source row
   const int row = have + j;          // destination row
   if (chunk >= chunks || j >= add || row >= M) return;  // (rows at or beyond the capacity are dropped)
@@ -47,8 +45,8 @@ __global__ __launch_bounds__(256) void append_rows_kernel(AppendArgs a, const in
 __global__ void append_counts_kernel(int32_t* __restrict__ n_valid, const int32_t* __restrict__ n_new, int n_tasks, int N, int M) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= n_tasks) return;
-  const int have = ap_clamp(n_valid[b], M);
-  const int add = n_new ? ap_clamp(n_new[b], N) : N;
+  const int have = clamp_count(n_valid, b, M);
+  const int add = n_new ? clamp_count(n_new, b, N) : N;
   n_valid[b] = have + add < M ? have + add : M;
 }
 

@@ -12,27 +12,45 @@ constexpr float kHalfLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
 
 __device__ __forceinline__ float softplus_grad(float x) { return x > 20.f ? 1.f : 1.f / (1.f + expf(-x)); }
 
-__global__ __launch_bounds__(256) void gauss_head_fwd_kernel(const float* __restrict__ suff, int pts, int dy, int homosk,
-                                                             const float* __restrict__ Y, int n_y_rows,
-                                                             float* __restrict__ loc, float* __restrict__ scale,
+// pooled[d] = the mean over a row's first n points of term(t, d), for every output dimension d; in LDS for the whole workgroup
+template <class Term>
+__device__ __forceinline__ void pool_over_points(int n, int dy, float* pooled, float* red, Term term) {
+  const int step = blockDim.x;  // (read once: re-read inside the loops it costs two VGPRs)
+  for (int d = 0; d < dy; ++d) {
+    float part = 0.f;
+    for (int t = threadIdx.x; t < n; t += step) part += term(t, d);
+    const float tot = block_sum(part, red);
+    if (threadIdx.x == 0) pooled[d] = tot / (float)n;
+  }
+  __syncthreads();
+}
+
+// One forward and one backward kernel in two instances each.  MASKED = false (npf_gauss_head_fwd / _bwd): every row owns its pts
+// points; n_valid / n_tasks are not read.  MASKED = true (npf_masked_gauss_head_fwd / _bwd): padded targets, row r owns the first
+// n_valid[r % n_tasks] of its pts points (clamped to [0, pts]).  n_valid is a DEVICE int32 [n_tasks] tensor, so the launch can sit in a
+// captured graph and see new counts at every replay.  Every loop over the points is bounded by the count: a task with few targets
+// costs few iterations and suff / Y beyond the count are never read (NaN there is harmless).  Both instances run the same loops in
+// the same order: full counts give the unmasked results bit for bit.
+// Forward, beyond the count: loc = 0, scale = 1 (a valid Normal); the homoskedastic pooling divides by the count.
+// Backward: EVERY row of d_suff is written, the rows at and beyond the count as zeros.  That is what keeps the rest of the backward
+// pass correct without further masks: the decoder's dgrad of a zero row is zero, so the weight gradients, dO of the attention and
+// with it dK / dV, and the x-encoder's gradients get nothing from padding.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void gauss_head_fwd_kernel(const float* __restrict__ suff, const int32_t* __restrict__ n_valid,
+                                                             int n_tasks, int pts, int dy, int homosk, const float* __restrict__ Y,
+                                                             int n_y_rows, float* __restrict__ loc, float* __restrict__ scale,
                                                              float* __restrict__ sum_logp) {
   __shared__ float red[8];
   __shared__ float pooled[32];
   const size_t row = blockIdx.x;
+  const int nv = MASKED ? clamp_count(n_valid, row % (size_t)n_tasks, pts) : pts;  // (uniform over the workgroup)
   const float* s = suff + row * pts * (size_t)(2 * dy);
   float* lo = loc + row * pts * (size_t)dy;
   float* sc = scale + row * pts * (size_t)dy;
   const float* y = Y ? Y + (row % n_y_rows) * pts * (size_t)dy : nullptr;
-  const int n = pts * dy;
-  if (homosk) {
-    for (int d = 0; d < dy; ++d) {
-      float part = 0.f;
-      for (int t = threadIdx.x; t < pts; t += blockDim.x) part += 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
-      const float tot = block_sum(part, red);
-      if (threadIdx.x == 0) pooled[d] = tot / (float)pts;
-    }
-    __syncthreads();
-  }
+  const int n = nv * dy;
+  if (homosk && (!MASKED || nv > 0))
+    pool_over_points(nv, dy, pooled, red, [&](int t, int d) { return 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]); });
   float lp = 0.f;
   for (int e = threadIdx.x; e < n; e += blockDim.x) {
     const int t = e / dy, d = e - t * dy;
@@ -47,130 +65,12 @@ __global__ __launch_bounds__(256) void gauss_head_fwd_kernel(const float* __rest
       lp += -(diff * diff) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
     }
   }
-  if (sum_logp) {
-    const float tot = block_sum(lp, red);
-    if (threadIdx.x == 0) sum_logp[row] = tot;
-  }
-}
-
-__global__ __launch_bounds__(256) void gauss_head_bwd_kernel(const float* __restrict__ suff, const float* __restrict__ loc,
-                                                             const float* __restrict__ scale, int pts, int dy, int homosk,
-                                                             const float* __restrict__ Y, int n_y_rows,
-                                                             const float* __restrict__ d_loc, const float* __restrict__ d_scale,
-                                                             const float* __restrict__ d_sum_logp, float* __restrict__ d_suff) {
-  __shared__ float red[8];
-  __shared__ float pooled[32];
-  const size_t row = blockIdx.x;
-  const size_t ebase = row * pts * (size_t)dy;
-  const float* s = suff + row * pts * (size_t)(2 * dy);
-  float* ds = d_suff + row * pts * (size_t)(2 * dy);
-  const float* y = Y ? Y + (row % n_y_rows) * pts * (size_t)dy : nullptr;
-  const float g = (d_sum_logp && y) ? d_sum_logp[row] : 0.f;
-  const int n = pts * dy;
-  // loc / scale NULL (the forward pass was a loss-only launch): recomputed from the raw decoder output
-  __shared__ float pooled_sg[32];
-  if (!scale && homosk) {
-    for (int d = 0; d < dy; ++d) {
-      float part = 0.f;
-      for (int t = threadIdx.x; t < pts; t += blockDim.x) part += 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
-      const float tot = block_sum(part, red);
-      if (threadIdx.x == 0) pooled_sg[d] = tot / (float)pts;
-    }
-    __syncthreads();
-  }
-  auto mu_of = [&](int e, int t, int d) { return loc ? loc[ebase + e] : s[t * 2 * dy + d]; };
-  auto sg_of = [&](int e, int t, int d) {
-    return scale ? scale[ebase + e] : (homosk ? pooled_sg[d] : 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]));
-  };
-  if (homosk) {
-    for (int d = 0; d < dy; ++d) {
-      float part = 0.f;
-      for (int t = threadIdx.x; t < pts; t += blockDim.x) {
-        const int e = t * dy + d;
-        const float sg = sg_of(e, t, d);
-        float dsg = d_scale ? d_scale[ebase + e] : 0.f;
-        if (y) {
-          const float diff = y[e] - mu_of(e, t, d);
-          dsg += g * (diff * diff / (sg * sg * sg) - 1.f / sg);
-        }
-        part += dsg;
-      }
-      const float tot = block_sum(part, red);
-      if (threadIdx.x == 0) pooled[d] = tot / (float)pts;
-    }
-    __syncthreads();
-  }
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    const int t = e / dy, d = e - t * dy;
-    const float mu = mu_of(e, t, d), sg = sg_of(e, t, d);
-    float dmu = d_loc ? d_loc[ebase + e] : 0.f;
-    float dsg = d_scale ? d_scale[ebase + e] : 0.f;
-    if (y) {
-      const float diff = y[e] - mu;
-      dmu += g * diff / (sg * sg);
-      dsg += g * (diff * diff / (sg * sg * sg) - 1.f / sg);
-    }
-    if (homosk) dsg = pooled[d];
-    ds[t * 2 * dy + d] = dmu;
-    ds[t * 2 * dy + dy + d] = dsg * 0.99f * softplus_grad(s[t * 2 * dy + dy + d]);
-  }
-}
-
-// ---- padded targets: the head of a batch whose task b owns the first n_valid[b] of its pts target rows -------------------------
-// (npf_masked_gauss_head_fwd / _bwd).  n_valid is a DEVICE int32 [n_tasks] tensor (row r reads n_valid[r % n_tasks], clamped to
-// [0, pts]), so the launch can sit in a captured graph and see new counts at every replay.  Every loop over the points is bounded by
-// the count: a task with few targets costs few iterations and suff / Y beyond the count are never read (NaN there is harmless).
-// Forward: loc / scale / sum_logp / the homoskedastic pooling (divided by the count) over the rows below the count, in the order
-// of gauss_head_fwd_kernel -- full counts give its results bit for bit; rows beyond: loc = 0, scale = 1 (a valid Normal).
-// Backward: EVERY row of d_suff is written, the rows at and beyond the count as zeros.  That is what keeps the rest of the backward
-// pass correct without further masks: the decoder's dgrad of a zero row is zero, so the weight gradients, dO of the attention and
-// with it dK / dV, and the x-encoder's gradients get nothing from padding.
-__device__ __forceinline__ int head_count(const int32_t* __restrict__ n_valid, size_t row, int n_tasks, int pts) {
-  const int n = n_valid[row % (size_t)n_tasks];
-  return n < 0 ? 0 : (n > pts ? pts : n);
-}
-
-__global__ __launch_bounds__(256) void masked_gauss_head_fwd_kernel(const float* __restrict__ suff,
-                                                                    const int32_t* __restrict__ n_valid, int n_tasks, int pts, int dy,
-                                                                    int homosk, const float* __restrict__ Y, int n_y_rows,
-                                                                    float* __restrict__ loc, float* __restrict__ scale,
-                                                                    float* __restrict__ sum_logp) {
-  __shared__ float red[8];
-  __shared__ float pooled[32];
-  const size_t row = blockIdx.x;
-  const int nv = head_count(n_valid, row, n_tasks, pts);  // (uniform over the workgroup)
-  const float* s = suff + row * pts * (size_t)(2 * dy);
-  float* lo = loc + row * pts * (size_t)dy;
-  float* sc = scale + row * pts * (size_t)dy;
-  const float* y = Y ? Y + (row % n_y_rows) * pts * (size_t)dy : nullptr;
-  const int n = nv * dy;
-  if (homosk && nv > 0) {
-    for (int d = 0; d < dy; ++d) {
-      float part = 0.f;
-      for (int t = threadIdx.x; t < nv; t += blockDim.x) part += 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
-      const float tot = block_sum(part, red);
-      if (threadIdx.x == 0) pooled[d] = tot / (float)nv;
-    }
-    __syncthreads();
-  }
-  float lp = 0.f;
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    const int t = e / dy, d = e - t * dy;
-    const float mu = s[t * 2 * dy + d];
-    const float sg = homosk ? pooled[d] : 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
+  if constexpr (MASKED) {
     if (loc) {
-      lo[e] = mu;
-      sc[e] = sg;
-    }
-    if (y) {
-      const float diff = y[e] - mu;
-      lp += -(diff * diff) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
-    }
-  }
-  if (loc) {
-    for (int e = n + threadIdx.x; e < pts * dy; e += blockDim.x) {
-      lo[e] = 0.f;
-      sc[e] = 1.f;
+      for (int e = n + threadIdx.x; e < pts * dy; e += blockDim.x) {
+        lo[e] = 0.f;
+        sc[e] = 1.f;
+      }
     }
   }
   if (sum_logp) {
@@ -179,56 +79,46 @@ __global__ __launch_bounds__(256) void masked_gauss_head_fwd_kernel(const float*
   }
 }
 
-__global__ __launch_bounds__(256) void masked_gauss_head_bwd_kernel(const float* __restrict__ suff, const float* __restrict__ loc,
-                                                                    const float* __restrict__ scale,
-                                                                    const int32_t* __restrict__ n_valid, int n_tasks, int pts, int dy,
-                                                                    int homosk, const float* __restrict__ Y, int n_y_rows,
-                                                                    const float* __restrict__ d_loc, const float* __restrict__ d_scale,
-                                                                    const float* __restrict__ d_sum_logp, float* __restrict__ d_suff) {
+template <bool MASKED>
+__global__ __launch_bounds__(256) void gauss_head_bwd_kernel(const float* __restrict__ suff, const float* __restrict__ loc,
+                                                             const float* __restrict__ scale, const int32_t* __restrict__ n_valid,
+                                                             int n_tasks, int pts, int dy, int homosk, const float* __restrict__ Y,
+                                                             int n_y_rows, const float* __restrict__ d_loc,
+                                                             const float* __restrict__ d_scale, const float* __restrict__ d_sum_logp,
+                                                             float* __restrict__ d_suff) {
   __shared__ float red[8];
   __shared__ float pooled[32];
   __shared__ float pooled_sg[32];
   const size_t row = blockIdx.x;
-  const int nv = head_count(n_valid, row, n_tasks, pts);  // (uniform over the workgroup)
+  const int nv = MASKED ? clamp_count(n_valid, row % (size_t)n_tasks, pts) : pts;  // (uniform over the workgroup)
   const size_t ebase = row * pts * (size_t)dy;
   const float* s = suff + row * pts * (size_t)(2 * dy);
   float* ds = d_suff + row * pts * (size_t)(2 * dy);
   const float* y = Y ? Y + (row % n_y_rows) * pts * (size_t)dy : nullptr;
   const float g = (d_sum_logp && y) ? d_sum_logp[row] : 0.f;
   const int n = nv * dy;
-  for (int i = 2 * n + threadIdx.x; i < pts * 2 * dy; i += blockDim.x) ds[i] = 0.f;  // the rows at and beyond the count
-  if (nv == 0) return;  // (ahead of every barrier)
-  if (!scale && homosk) {
-    for (int d = 0; d < dy; ++d) {
-      float part = 0.f;
-      for (int t = threadIdx.x; t < nv; t += blockDim.x) part += 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]);
-      const float tot = block_sum(part, red);
-      if (threadIdx.x == 0) pooled_sg[d] = tot / (float)nv;
-    }
-    __syncthreads();
+  if constexpr (MASKED) {
+    for (int i = 2 * n + threadIdx.x; i < pts * 2 * dy; i += blockDim.x) ds[i] = 0.f;  // the rows at and beyond the count
+    if (nv == 0) return;  // (ahead of every barrier)
   }
+  // loc / scale NULL (the forward pass was a loss-only launch): recomputed from the raw decoder output
+  if (!scale && homosk)
+    pool_over_points(nv, dy, pooled_sg, red, [&](int t, int d) { return 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]); });
   auto mu_of = [&](int e, int t, int d) { return loc ? loc[ebase + e] : s[t * 2 * dy + d]; };
   auto sg_of = [&](int e, int t, int d) {
     return scale ? scale[ebase + e] : (homosk ? pooled_sg[d] : 0.01f + 0.99f * softplus_t(s[t * 2 * dy + dy + d]));
   };
-  if (homosk) {
-    for (int d = 0; d < dy; ++d) {
-      float part = 0.f;
-      for (int t = threadIdx.x; t < nv; t += blockDim.x) {
-        const int e = t * dy + d;
-        const float sg = sg_of(e, t, d);
-        float dsg = d_scale ? d_scale[ebase + e] : 0.f;
-        if (y) {
-          const float diff = y[e] - mu_of(e, t, d);
-          dsg += g * (diff * diff / (sg * sg * sg) - 1.f / sg);
-        }
-        part += dsg;
+  if (homosk)
+    pool_over_points(nv, dy, pooled, red, [&](int t, int d) {
+      const int e = t * dy + d;
+      const float sg = sg_of(e, t, d);
+      float dsg = d_scale ? d_scale[ebase + e] : 0.f;
+      if (y) {
+        const float diff = y[e] - mu_of(e, t, d);
+        dsg += g * (diff * diff / (sg * sg * sg) - 1.f / sg);
       }
-      const float tot = block_sum(part, red);
-      if (threadIdx.x == 0) pooled[d] = tot / (float)nv;
-    }
-    __syncthreads();
-  }
+      return dsg;
+    });
   for (int e = threadIdx.x; e < n; e += blockDim.x) {
     const int t = e / dy, d = e - t * dy;
     const float mu = mu_of(e, t, d), sg = sg_of(e, t, d);
@@ -358,7 +248,7 @@ extern "C" int npf_gauss_head_fwd(const float* suff, int32_t n_rows, int32_t pts
   if (!loc && !sum_logp) return NPF_EINVAL;  // a launch that writes nothing
   if (Y && n_y_rows <= 0) return NPF_EINVAL;
   if (sum_logp && !Y) return NPF_EINVAL;
-  hipLaunchKernelGGL(npf::gauss_head_fwd_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, pts, dy,
+  hipLaunchKernelGGL(npf::gauss_head_fwd_kernel<false>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, nullptr, 0, pts, dy,
                      homoskedastic, Y, Y ? n_y_rows : 1, loc, scale, sum_logp);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
@@ -371,8 +261,8 @@ extern "C" int npf_gauss_head_bwd(const float* suff, const float* loc, const flo
   if ((loc == nullptr) != (scale == nullptr)) return NPF_EINVAL;
   if (!loc && (d_loc || d_scale)) return NPF_EINVAL;
   if (Y && n_y_rows <= 0) return NPF_EINVAL;
-  hipLaunchKernelGGL(npf::gauss_head_bwd_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, loc, scale, pts, dy,
-                     homoskedastic, Y, Y ? n_y_rows : 1, d_loc, d_scale, d_sum_logp, d_suff);
+  hipLaunchKernelGGL(npf::gauss_head_bwd_kernel<false>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, loc, scale, nullptr, 0,
+                     pts, dy, homoskedastic, Y, Y ? n_y_rows : 1, d_loc, d_scale, d_sum_logp, d_suff);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }
@@ -385,7 +275,7 @@ extern "C" int npf_masked_gauss_head_fwd(const float* suff, const int32_t* n_val
   if (!loc && !sum_logp) return NPF_EINVAL;  // a launch that writes nothing
   if (Y && (n_y_rows <= 0 || n_y_rows % n_tasks != 0)) return NPF_EINVAL;  // (rows that share a Y row share a count)
   if (sum_logp && !Y) return NPF_EINVAL;
-  hipLaunchKernelGGL(npf::masked_gauss_head_fwd_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, n_valid, n_tasks, pts,
+  hipLaunchKernelGGL(npf::gauss_head_fwd_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, n_valid, n_tasks, pts,
                      dy, homoskedastic, Y, Y ? n_y_rows : 1, loc, scale, sum_logp);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
@@ -400,7 +290,7 @@ extern "C" int npf_masked_gauss_head_bwd(const float* suff, const float* loc, co
   if ((loc == nullptr) != (scale == nullptr)) return NPF_EINVAL;
   if (!loc && (d_loc || d_scale)) return NPF_EINVAL;
   if (Y && (n_y_rows <= 0 || n_y_rows % n_tasks != 0)) return NPF_EINVAL;
-  hipLaunchKernelGGL(npf::masked_gauss_head_bwd_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, loc, scale, n_valid,
+  hipLaunchKernelGGL(npf::gauss_head_bwd_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, suff, loc, scale, n_valid,
                      n_tasks, pts, dy, homoskedastic, Y, Y ? n_y_rows : 1, d_loc, d_scale, d_sum_logp, d_suff);
   NPF_CHECK_LAUNCH();
   return NPF_OK;

@@ -1,6 +1,6 @@
 // Layout changes at the module boundary (row-major torch tensors <-> PT32), the weight
 // transpose used by the dgrad chains, and the mean aggregation over a task's points
-// (torch.mean(R_cntxt, dim=1): npf/neuralproc/np.py:95, attnnp.py:181).  All HBM-bound,
+// (torch.mean(R_cntxt, dim=1): npf/neuralproc/np.py:95, attnnp.py:181; of a padded batch: over each task's count).  All HBM-bound,
 // one float4 per thread, coalesced on the PT32 side.
 #include "npf_common.hpp"
 
@@ -184,29 +184,37 @@ __global__ void prepare_weights_kernel(const WprepJobs J) {
   }
 }
 
-// out[task][f] = mean over valid points.  grid = (ceil(F/32), n_tasks); 256 threads = 8 feature quads x 32 points.
-__global__ void mean_agg_fwd_kernel(const float* __restrict__ R, int pts, int F, float* __restrict__ out) {
+// out[task][f] = mean over the task's points.  grid = (F / 32, n_tasks); 256 threads = 8 feature quads x 32 points.
+// One forward and one backward kernel in two instances each.  MASKED = false (npf_mean_agg_fwd / _bwd): all pts points; n_valid is
+// not read.  MASKED = true (npf_masked_mean_fwd / _bwd): the first n_valid[task] points (a device int32 count, clamped to [0, pts];
+// zeros for a task without any) -- tiles beyond the count are not read.  The same thread mapping and summation order in both: full
+// counts give the unmasked result bit for bit.
+template <bool MASKED>
+__global__ void mean_fwd_kernel(const float* __restrict__ R, const int32_t* __restrict__ n_valid, int pts, int F,
+                                float* __restrict__ out) {
   const int tiles = (pts + 31) / 32;
   const int p = threadIdx.x & 31, f4 = blockIdx.x * 8 + (threadIdx.x >> 5);
   const size_t task = blockIdx.y;
+  const int n = MASKED ? clamp_count(n_valid, task, pts) : pts;
+  const bool in_F = MASKED || f4 < F / 4;
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (f4 < F / 4) {
+  if (in_F) {
     const float* base = R + task * tiles * (size_t)(F * 32) + pt_off(f4, p);
-    for (int t = 0; t < tiles; ++t)
-      if (t * 32 + p < pts) s += *(const f32x4*)(base + (size_t)t * F * 32);
+    for (int t = 0; t * 32 < n; ++t)
+      if (t * 32 + p < n) s += *(const f32x4*)(base + (size_t)t * F * 32);
   }
 #pragma unroll
   for (int off = 16; off >= 1; off >>= 1)
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] += __shfl_xor(s[j], off);
-  if (p == 0 && f4 < F / 4) *(f32x4*)(out + task * F + 4 * f4) = s * (1.f / (float)pts);
+  if (p == 0 && in_F) *(f32x4*)(out + task * F + 4 * f4) = (!MASKED || n > 0) ? s * (1.f / (float)n) : f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-__global__ void mean_agg_bwd_kernel(const float* __restrict__ d_out, int n_tasks, int pts, int F, float* __restrict__ dR,
-                                    int accumulate) {
+template <bool MASKED>
+__global__ void mean_bwd_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ n_valid, int n_tasks, int pts, int F,
+                                float* __restrict__ dR, int accumulate) {
   const int tiles = (pts + 31) / 32;
   const size_t total = (size_t)n_tasks * tiles * (F / 4) * 32;
-  const float inv = 1.f / (float)pts;
   for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int p = idx & 31;
     const size_t r = idx >> 5;
@@ -214,8 +222,9 @@ __global__ void mean_agg_bwd_kernel(const float* __restrict__ d_out, int n_tasks
     const size_t tt = r / (F / 4);
     const int tile = tt % tiles;
     const size_t task = tt / tiles;
+    const int n = MASKED ? clamp_count(n_valid, task, pts) : pts;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (tile * 32 + p < pts) v = *(const f32x4*)(d_out + task * F + 4 * f4) * inv;
+    if (tile * 32 + p < n) v = *(const f32x4*)(d_out + task * F + 4 * f4) * (1.f / (float)n);
     if (accumulate) v += *(const f32x4*)(dR + idx * 4);
     *(f32x4*)(dR + idx * 4) = v;
   }
@@ -337,7 +346,8 @@ extern "C" int npf_merge_heads(const float* src, int32_t n_tasks, int32_t pts, i
 
 extern "C" int npf_mean_agg_fwd(const float* R_pt, int32_t n_tasks, int32_t pts, int32_t F, float* out, void* stream) {
   if (!R_pt || !out || n_tasks <= 0 || pts <= 0 || F <= 0 || (F & 31)) return NPF_EINVAL;
-  hipLaunchKernelGGL(npf::mean_agg_fwd_kernel, dim3(F / 32, n_tasks), dim3(256), 0, (hipStream_t)stream, R_pt, pts, F, out);
+  hipLaunchKernelGGL(npf::mean_fwd_kernel<false>, dim3(F / 32, n_tasks), dim3(256), 0, (hipStream_t)stream, R_pt, nullptr, pts, F,
+                     out);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }
@@ -346,7 +356,29 @@ extern "C" int npf_mean_agg_bwd(const float* d_out, int32_t n_tasks, int32_t pts
                                 int32_t accumulate, void* stream) {
   if (!d_out || !dR_pt || n_tasks <= 0 || pts <= 0 || F <= 0 || (F & 31)) return NPF_EINVAL;
   const size_t total = (size_t)n_tasks * ((pts + 31) / 32) * (F / 4) * 32;
-  hipLaunchKernelGGL(npf::mean_agg_bwd_kernel, dim3(npf::grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, d_out,
+  hipLaunchKernelGGL(npf::mean_bwd_kernel<false>, dim3(npf::grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, d_out,
+                     nullptr, n_tasks, pts, F, dR_pt, accumulate);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_mean_fwd(const float* R_pt, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* out,
+                                   void* stream) {
+  if (!R_pt || !n_valid || !out || n_tasks < 0 || pts <= 0 || F <= 0 || (F & 31)) return NPF_EINVAL;
+  if ((((uintptr_t)R_pt) | ((uintptr_t)out)) & 15) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  hipLaunchKernelGGL(npf::mean_fwd_kernel<true>, dim3(F / 32, n_tasks), dim3(256), 0, (hipStream_t)stream, R_pt, n_valid, pts, F, out);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_mean_bwd(const float* d_out, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* dR_pt,
+                                   int32_t accumulate, void* stream) {
+  if (!d_out || !n_valid || !dR_pt || n_tasks < 0 || pts <= 0 || F <= 0 || (F & 31)) return NPF_EINVAL;
+  if ((((uintptr_t)d_out) | ((uintptr_t)dR_pt)) & 15) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  const size_t total = (size_t)n_tasks * ((pts + 31) / 32) * (F / 4) * 32;
+  hipLaunchKernelGGL(npf::mean_bwd_kernel<true>, dim3(npf::grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, d_out, n_valid,
                      n_tasks, pts, F, dR_pt, accumulate);
   NPF_CHECK_LAUNCH();
   return NPF_OK;

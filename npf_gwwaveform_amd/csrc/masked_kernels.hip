@@ -1,10 +1,10 @@
-// Attention and mean over PADDED contexts whose real sizes are data on the device (npf_masked_attn_fwd / _bwd, npf_masked_mean_fwd /
-// _bwd): every task b has n_valid[b] real context points out of the n_keys rows its tensors hold, and n_valid is an int32 tensor the
-// kernels read -- the host never does, so a launch can sit in a captured graph and see new counts at every replay.
+// Attention over PADDED contexts whose real sizes are data on the device (npf_masked_attn_fwd / _bwd): every task b has n_valid[b]
+// real context points out of the n_keys rows its tensors hold, and n_valid is an int32 tensor the kernels read -- the host never
+// does, so a launch can sit in a captured graph and see new counts at every replay.  (The mean over such a context,
+// npf_masked_mean_fwd / _bwd, is the MASKED instance of the mean kernels in layout_kernels.hip.)
 //
-// What they compute, in the reference's terms: DotAttender.forward (npf/architectures/attention.py:129-164, 204-220) and
-// torch.mean(R_cntxt, dim=1) (npf/neuralproc/np.py:95, attnnp.py:181) of the batch whose task b was cut to its first n_valid[b]
-// context points.
+// What they compute, in the reference's terms: DotAttender.forward (npf/architectures/attention.py:129-164, 204-220) of the batch
+// whose task b was cut to its first n_valid[b] context points.
 //
 // Attention: scaled-dot, one head, feature widths d = 4 ... 256 (heads of a multihead attention come as extra tasks, npf_split_heads).
 // fp32 throughout on v_mfma_f32_16x16x4_f32 with the operand roles of mha_kernel.hip (the first contraction TRANSPOSED, so the
@@ -41,12 +41,6 @@ __device__ __forceinline__ float mk_max4(float v) {
   v = fmaxf(v, __shfl_xor(v, 16));
   v = fmaxf(v, __shfl_xor(v, 32));
   return v;
-}
-
-// the task's count, clamped to what its tensors hold
-__device__ __forceinline__ int mk_count(const int32_t* __restrict__ n_valid, int b, int n_keys) {
-  const int n = n_valid[b];
-  return n < 0 ? 0 : (n > n_keys ? n_keys : n);
 }
 
 // rows key0 .. key0 + KB - 1 of a task's PT32 tensor into LDS, LD floats apart (LD even); rows >= nv and features >= d as zeros
@@ -87,8 +81,8 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
   const int qblocks = (T + 63) >> 6;
   const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
   const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
-  const int nv = mk_count(n_valid, b, n_keys);
-  const int nq = NQ ? mk_count(n_q_valid, b, T) : T;
+  const int nv = clamp_count(n_valid, b, n_keys);
+  const int nq = NQ ? clamp_count(n_q_valid, b, T) : T;
   const int q = qb * 64 + wave * 16 + c;
   if (NQ && qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zeros, no key staged
     if (q < tilesT * 32) {
@@ -174,8 +168,8 @@ __global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __rest
   const int qblocks = (T + 63) >> 6;
   const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
   const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
-  const int nv = mk_count(n_valid, b, n_keys);
-  const int nq = NQ ? mk_count(n_q_valid, b, T) : T;
+  const int nv = clamp_count(n_valid, b, n_keys);
+  const int nq = NQ ? clamp_count(n_q_valid, b, T) : T;
   const int q = qb * 64 + wave * 16 + c;
   if (NQ && qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zero d_q rows
     if (q < tilesT * 32) {
@@ -256,8 +250,8 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
   const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
   const int kblocks = 2 * tilesC;  // (whole tiles: every row of d_k / d_v is written)
   const int kb = blockIdx.x % kblocks, b = blockIdx.x / kblocks;
-  const int nv = mk_count(n_valid, b, n_keys);
-  const int nq = NQ ? mk_count(n_q_valid, b, T) : T;  // (uniform over the workgroup)
+  const int nv = clamp_count(n_valid, b, n_keys);
+  const int nq = NQ ? clamp_count(n_q_valid, b, T) : T;  // (uniform over the workgroup)
   const int key0 = 16 * kb;
   if (key0 >= nv) {  // (uniform over the workgroup)
     for (int i = tid; i < 16 * (Fp >> 2); i += 256) {
@@ -328,44 +322,6 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
         *(f32x4*)((pass == 0 ? dK : dV) + mk_pt(b, tilesC, Fp, key0 + c, 16 * dt + 4 * g)) = t;
       }
     }
-  }
-}
-
-// out[task][f] = mean over the first n_valid[task] points.  grid = (F / 32, n_tasks); 256 threads = 8 feature quads x 32 points;
-// tiles beyond the count are not read.
-__global__ void masked_mean_fwd_kernel(const float* __restrict__ R, const int32_t* __restrict__ n_valid, int pts, int F,
-                                       float* __restrict__ out) {
-  const int tiles = (pts + 31) / 32;
-  const int p = threadIdx.x & 31, f4 = blockIdx.x * 8 + (threadIdx.x >> 5);
-  const size_t task = blockIdx.y;
-  const int nv = mk_count(n_valid, (int)task, pts);
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  const float* base = R + task * tiles * (size_t)(F * 32) + pt_off(f4, p);
-  for (int t = 0; t * 32 < nv; ++t)
-    if (t * 32 + p < nv) s += *(const f32x4*)(base + (size_t)t * F * 32);
-#pragma unroll
-  for (int off = 16; off >= 1; off >>= 1)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s[j] += __shfl_xor(s[j], off);
-  if (p == 0) *(f32x4*)(out + task * F + 4 * f4) = nv > 0 ? s * (1.f / (float)nv) : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-__global__ void masked_mean_bwd_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ n_valid, int n_tasks, int pts,
-                                       int F, float* __restrict__ dR, int accumulate) {
-  const int tiles = (pts + 31) / 32;
-  const size_t total = (size_t)n_tasks * tiles * (F / 4) * 32;
-  for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int p = idx & 31;
-    const size_t r = idx >> 5;
-    const int f4 = r % (F / 4);
-    const size_t tt = r / (F / 4);
-    const int tile = tt % tiles;
-    const size_t task = tt / tiles;
-    const int nv = mk_count(n_valid, (int)task, pts);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (tile * 32 + p < nv) v = *(const f32x4*)(d_out + task * F + 4 * f4) * (1.f / (float)nv);
-    if (accumulate) v += *(const f32x4*)(dR + idx * 4);
-    *(f32x4*)(dR + idx * 4) = v;
   }
 }
 
@@ -491,27 +447,4 @@ extern "C" int npf_masked_attn_bwd_nq(const float* q, const float* k, const floa
                                       float* d_k, float* d_v, void* stream) {
   if (!n_q_valid) return NPF_EINVAL;
   return masked_attn_bwd(q, k, v, n_valid, n_q_valid, out, d_out, lse, n_tasks, n_keys, n_queries, d, scale, d_q, d_k, d_v, stream);
-}
-
-extern "C" int npf_masked_mean_fwd(const float* R_pt, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* out,
-                                   void* stream) {
-  if (!R_pt || !n_valid || !out || n_tasks < 0 || pts <= 0 || F <= 0 || (F & 31) || mk_misaligned(R_pt, out)) return NPF_EINVAL;
-  if (n_tasks == 0) return NPF_OK;
-  hipLaunchKernelGGL(npf::masked_mean_fwd_kernel, dim3(F / 32, n_tasks), dim3(256), 0, (hipStream_t)stream, R_pt, n_valid, pts, F,
-                     out);
-  NPF_CHECK_LAUNCH();
-  return NPF_OK;
-}
-
-extern "C" int npf_masked_mean_bwd(const float* d_out, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* dR_pt,
-                                   int32_t accumulate, void* stream) {
-  if (!d_out || !n_valid || !dR_pt || n_tasks < 0 || pts <= 0 || F <= 0 || (F & 31) || mk_misaligned(d_out, dR_pt)) return NPF_EINVAL;
-  if (n_tasks == 0) return NPF_OK;
-  const size_t total = (size_t)n_tasks * ((pts + 31) / 32) * (F / 4) * 32;
-  size_t g = (total + 255) / 256;
-  if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(npf::masked_mean_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, d_out, n_valid, n_tasks, pts,
-                     F, dR_pt, accumulate);
-  NPF_CHECK_LAUNCH();
-  return NPF_OK;
 }

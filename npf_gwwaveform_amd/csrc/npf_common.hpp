@@ -17,6 +17,12 @@ __host__ __device__ inline int pt_off(int f4, int p) { return (f4 * 32 + p) * 4;
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// Entry i of a device tensor of per-task counts, clamped to [0, hi], the rows the task's tensors hold (the host never reads a count)
+__device__ __forceinline__ int clamp_count(const int32_t* __restrict__ n, size_t i, int hi) {
+  const int v = n[i];
+  return v < 0 ? 0 : (v > hi ? hi : v);
+}
+
 #define NPF_CHECK_LAUNCH()                     \
   do {                                         \
     hipError_t e__ = hipGetLastError();        \

@@ -35,11 +35,7 @@ __global__ __launch_bounds__(THREADS) void mixture_summary_kernel(const float* _
   __shared__ double pooled_d[kMixMaxNz * kMixMaxDy];  // ... before its rounding to fp32 (the collapsed bracket below)
   __shared__ float comp[IN_LDS ? 2 * NZ * THREADS : 1];
   const int b = blockIdx.y;
-  int nv = pts;
-  if (n_valid) {
-    nv = n_valid[b];
-    nv = nv < 0 ? 0 : (nv > pts ? pts : nv);
-  }
+  const int nv = n_valid ? clamp_count(n_valid, b, pts) : pts;
   const size_t row_stride = (size_t)pts * (size_t)(2 * dy);  // floats of one (z-sample, task) row of suff
   const float* s_task = suff + (size_t)b * row_stride;         // row k of this task: + k * n_tasks * row_stride
   const size_t k_stride = (size_t)n_tasks * row_stride;

@@ -68,86 +68,46 @@ def sum_points_pt(pt: torch.Tensor, pts: int, F: int) -> torch.Tensor:
     return out * float(pts)
 
 
-class _MeanAggFn(torch.autograd.Function):
+class _MeanFn(torch.autograd.Function):
+    """Mean over all points of every task (``n_valid`` None: ``npf_mean_agg_fwd`` / ``_bwd``) or over the first ``n_valid[task]`` of
+    them (a device int32 tensor: ``npf_masked_mean_fwd`` / ``_bwd``)."""
+
     @staticmethod
-    def forward(ctx, pt, pts, F):
-        n_tasks, Fp = pt.shape[0], pad32(F)
+    def forward(ctx, pt, n_valid, n_tasks, pts, F):
+        Fp = pad32(F)
         ctx.geo = (n_tasks, pts, Fp)
+        if n_valid is not None:
+            ctx.save_for_backward(n_valid)
         out = torch.empty((n_tasks, Fp), dtype=torch.float32, device=pt.device)
-        L.check(L.load().npf_mean_agg_fwd(L.ptr(pt.contiguous()), n_tasks, pts, Fp, L.ptr(out), L.stream_ptr()),
-                "npf_mean_agg_fwd")
+        name, counts = ("npf_mean_agg_fwd", ()) if n_valid is None else ("npf_masked_mean_fwd", (_iptr(n_valid),))
+        L.check(getattr(L.load(), name)(L.ptr(pt.contiguous()), *counts, n_tasks, pts, Fp, L.ptr(out), L.stream_ptr()), name)
         return out
 
     @staticmethod
     def backward(ctx, g):
         n_tasks, pts, Fp = ctx.geo
         d = pt_empty(n_tasks, pts, Fp, g.device)
-        L.check(L.load().npf_mean_agg_bwd(L.ptr(g.contiguous()), n_tasks, pts, Fp, L.ptr(d), 0, L.stream_ptr()),
-                "npf_mean_agg_bwd")
-        return d, None, None
+        name, counts = ("npf_masked_mean_bwd", (_iptr(ctx.saved_tensors[0]),)) if ctx.saved_tensors else ("npf_mean_agg_bwd", ())
+        L.check(getattr(L.load(), name)(L.ptr(g.contiguous()), *counts, n_tasks, pts, Fp, L.ptr(d), 0, L.stream_ptr()), name)
+        return d, None, None, None, None
 
 
 def mean_agg(pt: torch.Tensor, pts: int, F: int) -> torch.Tensor:
     """torch.mean(R, dim=1) of a PT32 tensor -> row-major [n_tasks, pad32(F)]
     (npf/neuralproc/np.py:95, attnnp.py:181)."""
-    return _MeanAggFn.apply(pt, pts, F)
+    return _MeanFn.apply(pt, None, pt.shape[0], pts, F)
 
 
 # ---- Gaussian head --------------------------------------------------------------------
 class _GaussHeadFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, suff, Y, dy, homosk, want_dist):
-        n_rows, pts, two_dy = suff.shape
-        assert two_dy == 2 * dy
-        suff = suff.contiguous()
-        loc = scale = None
-        if want_dist:
-            loc = torch.empty((n_rows, pts, dy), dtype=torch.float32, device=suff.device)
-            scale = torch.empty_like(loc)
-        slp = None
-        n_y = 0
-        if Y is not None:
-            Y = Y.contiguous()
-            n_y = Y.shape[0]
-            assert Y.shape[1:] == (pts, dy) and n_rows % n_y == 0
-            slp = torch.empty((n_rows,), dtype=torch.float32, device=suff.device)
-        elif not want_dist:
-            raise ValueError("a loss-only head launch needs the targets")
-        L.check(L.load().npf_gauss_head_fwd(L.ptr(suff), n_rows, pts, dy, int(homosk), L.ptr(Y), n_y, L.ptr(loc),
-                                            L.ptr(scale), L.ptr(slp), L.stream_ptr()), "npf_gauss_head_fwd")
-        ctx.save_for_backward(suff, loc, scale, Y)
-        ctx.cfg = (dy, homosk)
-        empty = suff.new_zeros((0,))
-        outs = [loc if want_dist else empty, scale if want_dist else empty, slp if slp is not None else suff.new_zeros((n_rows,))]
-        nd = ([] if want_dist else [outs[0], outs[1]]) + ([] if slp is not None else [outs[2]])
-        if nd:
-            ctx.mark_non_differentiable(*nd)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, d_loc, d_scale, d_slp):
-        suff, loc, scale, Y = ctx.saved_tensors
-        dy, homosk = ctx.cfg
-        n_rows, pts, _ = suff.shape
-        d_suff = torch.empty_like(suff)
-        c = lambda t: t.contiguous() if t is not None else None  # noqa: E731
-        if loc is None:
-            d_loc = d_scale = None
-        L.check(L.load().npf_gauss_head_bwd(L.ptr(suff), L.ptr(loc), L.ptr(scale), n_rows, pts, dy, int(homosk),
-                                            L.ptr(Y), Y.shape[0] if Y is not None else 0, L.ptr(c(d_loc)),
-                                            L.ptr(c(d_scale)), L.ptr(c(d_slp)) if Y is not None else None,
-                                            L.ptr(d_suff), L.stream_ptr()), "npf_gauss_head_bwd")
-        return d_suff, None, None, None, None
-
-
-class _MaskedGaussHeadFn(torch.autograd.Function):
-    """``_GaussHeadFn`` over padded targets: row ``r`` owns its first ``n_valid[r % n_tasks]`` points (``npf_masked_gauss_head_fwd`` /
-    ``_bwd``).  Beyond the count: loc = 0, scale = 1, nothing in ``sum_log_prob``, zero rows in the gradient."""
+    """The head of every row over all its points (``n_valid`` None: ``npf_gauss_head_fwd`` / ``_bwd``) or over padded targets, row
+    ``r`` owning its first ``n_valid[r % n_tasks]`` points (a device int32 tensor: ``npf_masked_gauss_head_fwd`` / ``_bwd``).  Beyond
+    the count: loc = 0, scale = 1, nothing in ``sum_log_prob``, zero rows in the gradient."""
 
     @staticmethod
     def forward(ctx, suff, Y, n_valid, dy, homosk, want_dist):
         n_rows, pts, two_dy = suff.shape
-        n_tasks = n_valid.shape[0]
+        n_tasks = 1 if n_valid is None else n_valid.shape[0]
         assert two_dy == 2 * dy and n_rows % n_tasks == 0
         suff = suff.contiguous()
         loc = scale = None
@@ -163,9 +123,10 @@ class _MaskedGaussHeadFn(torch.autograd.Function):
             slp = torch.empty((n_rows,), dtype=torch.float32, device=suff.device)
         elif not want_dist:
             raise ValueError("a loss-only head launch needs the targets")
-        L.check(L.load().npf_masked_gauss_head_fwd(L.ptr(suff), _iptr(n_valid), n_tasks, n_rows, pts, dy, int(homosk), L.ptr(Y), n_y,
-                                                   L.ptr(loc), L.ptr(scale), L.ptr(slp), L.stream_ptr()), "npf_masked_gauss_head_fwd")
-        ctx.save_for_backward(suff, loc, scale, Y, n_valid)
+        name, counts = ("npf_gauss_head_fwd", ()) if n_valid is None else ("npf_masked_gauss_head_fwd", (_iptr(n_valid), n_tasks))
+        L.check(getattr(L.load(), name)(L.ptr(suff), *counts, n_rows, pts, dy, int(homosk), L.ptr(Y), n_y, L.ptr(loc), L.ptr(scale),
+                                        L.ptr(slp), L.stream_ptr()), name)
+        ctx.save_for_backward(suff, loc, scale, Y, *(() if n_valid is None else (n_valid,)))
         ctx.cfg = (dy, homosk)
         empty = suff.new_zeros((0,))
         outs = [loc if want_dist else empty, scale if want_dist else empty, slp if slp is not None else suff.new_zeros((n_rows,))]
@@ -176,17 +137,17 @@ class _MaskedGaussHeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loc, d_scale, d_slp):
-        suff, loc, scale, Y, n_valid = ctx.saved_tensors
+        suff, loc, scale, Y, *n_valid = ctx.saved_tensors
         dy, homosk = ctx.cfg
         n_rows, pts, _ = suff.shape
         d_suff = torch.empty_like(suff)  # (written whole: zeros beyond the count)
         c = lambda t: t.contiguous() if t is not None else None  # noqa: E731
         if loc is None:
             d_loc = d_scale = None
-        L.check(L.load().npf_masked_gauss_head_bwd(L.ptr(suff), L.ptr(loc), L.ptr(scale), _iptr(n_valid), n_valid.shape[0], n_rows,
-                                                   pts, dy, int(homosk), L.ptr(Y), Y.shape[0] if Y is not None else 0,
-                                                   L.ptr(c(d_loc)), L.ptr(c(d_scale)), L.ptr(c(d_slp)) if Y is not None else None,
-                                                   L.ptr(d_suff), L.stream_ptr()), "npf_masked_gauss_head_bwd")
+        name, counts = ("npf_masked_gauss_head_bwd", (_iptr(n_valid[0]), n_valid[0].shape[0])) if n_valid else ("npf_gauss_head_bwd", ())
+        L.check(getattr(L.load(), name)(L.ptr(suff), L.ptr(loc), L.ptr(scale), *counts, n_rows, pts, dy, int(homosk), L.ptr(Y),
+                                        Y.shape[0] if Y is not None else 0, L.ptr(c(d_loc)), L.ptr(c(d_scale)),
+                                        L.ptr(c(d_slp)) if Y is not None else None, L.ptr(d_suff), L.stream_ptr()), name)
         return d_suff, None, None, None, None, None
 
 
@@ -203,8 +164,8 @@ def gauss_head(suff: torch.Tensor, Y: Optional[torch.Tensor], dy: int, homoskeda
         n_tasks = n_valid.shape[0] if isinstance(n_valid, torch.Tensor) and n_valid.dim() == 1 else suff.shape[0]
         if suff.shape[0] % max(n_tasks, 1) != 0 or n_tasks == 0:
             raise ValueError(f"n_valid has {n_tasks} counts, the head {suff.shape[0]} rows (not a multiple)")
-        return _MaskedGaussHeadFn.apply(suff, Y, counts_i32(n_valid, n_tasks), dy, homoskedastic, want_dist)
-    return _GaussHeadFn.apply(suff, Y, dy, homoskedastic, want_dist)
+        n_valid = counts_i32(n_valid, n_tasks)
+    return _GaussHeadFn.apply(suff, Y, n_valid, dy, homoskedastic, want_dist)
 
 
 # ---- predictive summary over the latent samples -------------------------------------------
@@ -514,14 +475,10 @@ class _MaskedAttnFn(torch.autograd.Function):
         if CH.PROFILE is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        if n_q_valid is not None:  # (padded queries as well: the instances that skip them)
-            L.check(L.load().npf_masked_attn_fwd_nq(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), _iptr(n_q_valid), n_tasks,
-                                                    n_keys, n_queries, d, float(scale), L.ptr(out),
-                                                    L.ptr(lse) if lse is not None else None, L.stream_ptr()), "npf_masked_attn_fwd_nq")
-        else:
-            L.check(L.load().npf_masked_attn_fwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), n_tasks, n_keys, n_queries, d,
-                                                 float(scale), L.ptr(out), L.ptr(lse) if lse is not None else None, L.stream_ptr()),
-                    "npf_masked_attn_fwd")
+        # (n_q_valid: padded queries as well, the instances that skip them)
+        name, q_counts = ("npf_masked_attn_fwd", ()) if n_q_valid is None else ("npf_masked_attn_fwd_nq", (_iptr(n_q_valid),))
+        L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), *q_counts, n_tasks, n_keys, n_queries, d,
+                                        float(scale), L.ptr(out), L.ptr(lse) if lse is not None else None, L.stream_ptr()), name)
         if CH.PROFILE is not None:
             ev1.record()
             CH.PROFILE.append(("masked_attn_fwd_kernel", 4 * n_tasks * n_queries * n_keys * d, ev0, ev1,
@@ -543,14 +500,9 @@ class _MaskedAttnFn(torch.autograd.Function):
         if CH.PROFILE is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        if ctx.has_nq:
-            L.check(L.load().npf_masked_attn_bwd_nq(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), _iptr(ctx.saved_tensors[6]),
-                                                    L.ptr(out), L.ptr(g), L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq),
-                                                    L.ptr(dk), L.ptr(dv), L.stream_ptr()), "npf_masked_attn_bwd_nq")
-        else:
-            L.check(L.load().npf_masked_attn_bwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), L.ptr(out), L.ptr(g),
-                                                 L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk), L.ptr(dv),
-                                                 L.stream_ptr()), "npf_masked_attn_bwd")
+        name, q_counts = ("npf_masked_attn_bwd_nq", (_iptr(ctx.saved_tensors[6]),)) if ctx.has_nq else ("npf_masked_attn_bwd", ())
+        L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), *q_counts, L.ptr(out), L.ptr(g), L.ptr(lse),
+                                        n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.stream_ptr()), name)
         if CH.PROFILE is not None:
             ev1.record()
             CH.PROFILE.append(("masked_attn_bwd_kernels", 16 * n_tasks * n_queries * n_keys * d, ev0, ev1,
@@ -568,37 +520,15 @@ def masked_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor,
     rows below the counts are bit-identical to the call without it."""
     if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
         raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
-    if n_q_valid is None:
-        return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale)
-    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale,
-                               counts_i32(n_q_valid, n_tasks, "n_q_valid"))
-
-
-class _MaskedMeanFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pt, n_valid, n_tasks, pts, F):
-        Fp = pad32(F)
-        ctx.geo = (n_tasks, pts, Fp)
-        ctx.save_for_backward(n_valid)
-        out = torch.empty((n_tasks, Fp), dtype=torch.float32, device=pt.device)
-        L.check(L.load().npf_masked_mean_fwd(L.ptr(pt.contiguous()), _iptr(n_valid), n_tasks, pts, Fp, L.ptr(out), L.stream_ptr()),
-                "npf_masked_mean_fwd")
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        n_tasks, pts, Fp = ctx.geo
-        (n_valid,) = ctx.saved_tensors
-        d = pt_empty(n_tasks, pts, Fp, g.device)
-        L.check(L.load().npf_masked_mean_bwd(L.ptr(g.contiguous()), _iptr(n_valid), n_tasks, pts, Fp, L.ptr(d), 0, L.stream_ptr()),
-                "npf_masked_mean_bwd")
-        return d, None, None, None, None
+    if n_q_valid is not None:
+        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
+    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale, n_q_valid)
 
 
 def masked_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
     """Mean over the first ``n_valid[task]`` points of a PT32 tensor -> row-major [n_tasks, pad32(F)] (zeros where a task has none):
     ``torch.mean(R, dim=1)`` (npf/neuralproc/np.py:95, attnnp.py:181) of the batch cut per task; counts as in :func:`masked_attention`."""
-    return _MaskedMeanFn.apply(R_pt, counts_i32(n_valid, n_tasks), n_tasks, pts, F)
+    return _MeanFn.apply(R_pt, counts_i32(n_valid, n_tasks), n_tasks, pts, F)
 
 
 # ---- growing contexts: rows appended at per-task offsets that are device data (csrc/append_kernels.hip) ----------------------

@@ -123,7 +123,7 @@ class Conditioned:
         m = self._model
         with torch.no_grad():
             if n_trgt is not None:
-                n_trgt = m._check_n_trgt(n_trgt, X_trgt)
+                n_trgt = m._check_counts(n_trgt, X_trgt, "n_trgt")
             m._check_tensors(X_trgt)
             if X_trgt.dim() != 3 or X_trgt.shape[0] != self.B:
                 raise ValueError(f"X_trgt must be [B={self.B}, T, x_dim] (the batch the model was conditioned on), got {list(X_trgt.shape)}")
@@ -216,6 +216,12 @@ class Conditioned:
         return Y
 
 
+def _mean_rows(R_pt, pts, B, r, n_valid=None):
+    """Row-major [B, 1, r]: the mean over the ``pts`` points of every task of a PT32 tensor, or over the first ``n_valid[b]`` of them."""
+    m = FN.mean_agg(R_pt, pts, r) if n_valid is None else FN.masked_mean(R_pt, n_valid, B, pts, r)
+    return m[:, :r].reshape(B, 1, r)
+
+
 def _q_z_scale(z_scale):
     return 0.1 + 0.9 * torch.sigmoid(z_scale)
 
@@ -293,9 +299,9 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         the target-side mean of the latent path -- reads the counts.  With ``n_cntxt`` the masked attention also skips the
         queries beyond the count.  Not implemented with ``n_trgt``: ``is_self_attn=True`` and the bf16 compute mode."""
         if n_cntxt is not None:
-            n_cntxt = self._check_n_cntxt(n_cntxt, X_cntxt)
+            n_cntxt = self._check_counts(n_cntxt, X_cntxt, "n_cntxt")
         if n_trgt is not None:
-            n_trgt = self._check_n_trgt(n_trgt, X_trgt)
+            n_trgt = self._check_counts(n_trgt, X_trgt, "n_trgt")
         self._validate_inputs(X_cntxt, Y_cntxt, X_trgt, Y_trgt)
         B, C, _ = X_cntxt.shape
         T = X_trgt.shape[1]
@@ -368,10 +374,8 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
                 z_samples, q_zCc, q_zCct = None, None, None
             if self.encoded_path == "latent":
                 R = None
-            if padded:
-                suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=n_valid, n_q_valid=n_trgt)
-            else:
-                suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T)  # [n_z * B, T, 2 dy]
+            suff = self._target_suffstat(Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=n_valid,
+                                         n_q_valid=n_trgt if padded else None)  # [n_z * B, T, 2 dy]
         finally:
             self._X_trgt_raw = None
         return self._head(suff, Y_trgt, B, T, n_trgt=n_trgt), z_samples, q_zCc, q_zCct
@@ -391,7 +395,7 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         with torch.no_grad():
             n_z = self._n_z_for(n_z_samples)
             if n_cntxt is not None:
-                n_cntxt = self._check_n_cntxt(n_cntxt, X_cntxt)
+                n_cntxt = self._check_counts(n_cntxt, X_cntxt, "n_cntxt")
             self._check_tensors(X_cntxt, Y_cntxt)
             B, C, _ = X_cntxt.shape
             if n_z is not None:
@@ -413,12 +417,7 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         from them).  A latent model draws ``eps = randn([n_z, B, 1, z_dim])`` once -- the draw ``rsample`` makes in ``condition`` -- keeps
         it (``Conditioned.eps``) and sets ``z_samples = loc + scale * eps``, again after every ``extend``.  Not implemented, as with
         ``n_cntxt``: ``is_self_attn=True`` and the bf16 compute mode."""
-        from . import chain as _chain
-
-        if getattr(self, "is_self_attn", False):
-            raise NotImplementedError("capacity is not implemented for self-attention context encoders (is_self_attn=True)")
-        if _chain.COMPUTE_DTYPE != "fp32":
-            raise NotImplementedError("capacity is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
+        self._refuse_unimplemented("capacity")
         with torch.no_grad():
             n_z = self._n_z_for(n_z_samples)
             if X_cntxt.dim() != 3 or Y_cntxt.dim() != 3 or X_cntxt.shape[:2] != Y_cntxt.shape[:2]:
@@ -429,7 +428,7 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
                 raise ValueError(f"capacity={capacity} must be at least the context size C={C} (and at least 1)")
             self._check_tensors(X_cntxt, Y_cntxt)
             if n_cntxt is not None:
-                n_cntxt = self._check_n_cntxt(n_cntxt, X_cntxt)
+                n_cntxt = self._check_counts(n_cntxt, X_cntxt, "n_cntxt")
             if n_z is not None:
                 self.n_z_samples = n_z
             dev = X_cntxt.device
@@ -467,30 +466,22 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         probs = FN.check_probs(probs)
         return self.condition(X_cntxt, Y_cntxt, n_cntxt=n_cntxt, n_z_samples=n_z_samples).query(X_trgt, n_trgt=n_trgt).summary(probs)
 
-    def _check_n_cntxt(self, n_cntxt, X_cntxt):
-        """The per-task context sizes as a device int32 [B] tensor; refuses what the padded path does not implement."""
+    def _refuse_unimplemented(self, what):
+        """What the padded path does not implement (``what``: the argument that asks for it)."""
         from . import chain as _chain
 
         if getattr(self, "is_self_attn", False):
-            raise NotImplementedError("n_cntxt is not implemented for self-attention context encoders (is_self_attn=True)")
+            raise NotImplementedError(f"{what} is not implemented for self-attention context encoders (is_self_attn=True)")
         if _chain.COMPUTE_DTYPE != "fp32":
-            raise NotImplementedError("n_cntxt is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
-        n = FN.counts_i32(n_cntxt, X_cntxt.shape[0], "n_cntxt")
-        if n.device != X_cntxt.device:
-            raise ValueError(f"n_cntxt lives on {n.device}, the batch on {X_cntxt.device}")
-        return n
+            raise NotImplementedError(f"{what} is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
 
-    def _check_n_trgt(self, n_trgt, X_trgt):
-        """The per-task target sizes as a device int32 [B] tensor; refuses what the padded path does not implement."""
-        from . import chain as _chain
-
-        if getattr(self, "is_self_attn", False):
-            raise NotImplementedError("n_trgt is not implemented for self-attention context encoders (is_self_attn=True)")
-        if _chain.COMPUTE_DTYPE != "fp32":
-            raise NotImplementedError("n_trgt is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
-        n = FN.counts_i32(n_trgt, X_trgt.shape[0], "n_trgt")
-        if n.device != X_trgt.device:
-            raise ValueError(f"n_trgt lives on {n.device}, the batch on {X_trgt.device}")
+    def _check_counts(self, n, X, what):
+        """The per-task sizes ``what`` (``n_cntxt`` / ``n_trgt``) of the padded batch ``X`` as a device int32 [B] tensor; refuses what
+        the padded path does not implement."""
+        self._refuse_unimplemented(what)
+        n = FN.counts_i32(n, X.shape[0], what)
+        if n.device != X.device:
+            raise ValueError(f"{what} lives on {n.device}, the batch on {X.device}")
         return n
 
     def _validate_inputs(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt):
@@ -669,7 +660,7 @@ class LatentNeuralProcessFamily(NeuralProcessFamily):
 
     def _infer_q_zCc(self, R, B, n_valid=None):
         """q(z | C) from the context representation (``n_valid``: the context sizes of a padded batch)."""
-        return self._latent_dist_from(self._lat_input(R, B) if n_valid is None else self._lat_input(R, B, n_valid=n_valid))
+        return self._latent_dist_from(self._lat_input(R, B, n_valid=n_valid))
 
     def _latent_path_pt(self, R, C, Xt_pt, Y_trgt, B, T, n_valid=None, n_trgt=None):
         # (n_valid: the context sizes of a padded batch; n_trgt: the target sizes -- the target-side encode below pools over the
@@ -687,7 +678,7 @@ class LatentNeuralProcessFamily(NeuralProcessFamily):
                     R_t = self._encode_globally_pt(self._xenc_pt(self._X_trgt_raw), Y_trgt, B, T, n_valid=n_trgt)
             else:
                 R_t = self._encode_globally_pt(Xt_pt, Y_trgt, B, T, n_valid=n_trgt)
-            q_zCct = self._latent_dist_from(self._lat_input(R_t, B) if n_trgt is None else self._lat_input(R_t, B, n_valid=n_trgt))
+            q_zCct = self._latent_dist_from(self._lat_input(R_t, B, n_valid=n_trgt))
             sampling_dist = q_zCct
         else:
             q_zCct, sampling_dist = None, q_zCc
@@ -757,9 +748,7 @@ class CNP(NeuralProcessFamily):
     def _pool_pt(self, R_pts: PTensor, B, n_valid=None):
         """np.py:95: the mean over the context points of the per-point representations -> row-major [B, 1, r]; ``n_valid``: over
         the first ``n_valid[b]`` of them (a padded batch; zeros for a task without context, as ``encode_globally`` at C = 0)."""
-        if n_valid is not None:
-            return FN.masked_mean(R_pts.t, n_valid, B, R_pts.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
-        return FN.mean_agg(R_pts.t, R_pts.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
+        return _mean_rows(R_pts.t, R_pts.pts, B, self.r_dim, n_valid)
 
     def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None, n_q_valid=None):
         return self._decode_taskvec(Xt_pt, R.reshape(B, self.r_dim), B, T, B)
@@ -945,16 +934,14 @@ class AttnLNP(LatentNeuralProcessFamily, AttnCNP):
         B, C, _ = R.shape
         if C == 0:
             return torch.zeros(B, 1, self.r_dim, device=R.device)
-        return FN.mean_agg(FN.pack_pt(R), C, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
+        return _mean_rows(FN.pack_pt(R), C, B, self.r_dim)
 
     def _lat_input(self, R: Optional[PTensor], B, n_valid=None):
         """attnnp.py:172-181: the latent path pools the per-point representation (its own point count; ``n_valid``: the first
         ``n_valid[b]`` points of a padded batch)."""
         if R is None:
             return torch.zeros(B, 1, self.r_dim, device=self.r_z_merger.weight.device)
-        if n_valid is not None:
-            return FN.masked_mean(R.t, n_valid, B, R.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
-        return FN.mean_agg(R.t, R.pts, self.r_dim)[:, : self.r_dim].reshape(B, 1, self.r_dim)
+        return _mean_rows(R.t, R.pts, B, self.r_dim, n_valid)
 
     def trgt_dependent_representation(self, X_cntxt, z_samples, R, X_trgt):
         B, T, _ = X_trgt.shape

@@ -103,6 +103,32 @@ def test_masked_mean_matches_float64(C_pad, F):
             assert (out[b] == 0).all()
 
 
+@pytest.mark.parametrize("pts", (1, 31, 32, 33, 70))
+@pytest.mark.parametrize("F", (32, 96))
+def test_masked_mean_at_full_counts_is_the_unmasked_mean_bit_for_bit(F, pts):
+    """Counts at and above ``pts`` (clamped) against ``npf_mean_agg_fwd`` / ``_bwd``: the same thread mapping and summation order.
+    The sizes sit either side of the tile boundary (32 points) with a partly filled last tile; F = 96 gives three feature blocks."""
+    from npf_gwwaveform_amd import functional as FN
+
+    B = 3
+    g = torch.Generator().manual_seed(100 * F + pts)
+    R, w = torch.randn(B, pts, F, generator=g).to(DEV), torch.randn(B, F, generator=g).to(DEV)
+    n_valid = torch.tensor([pts, pts + 5, 10 ** 6], device=DEV)
+    outs = []
+    for mean in (lambda pt: FN.mean_agg(pt, pts, F), lambda pt: FN.masked_mean(pt, n_valid, B, pts, F)):
+        pt = FN.pack_pt(R).detach().requires_grad_(True)
+        with launch_witness() as wit:
+            out = mean(pt)
+            out.backward(w)
+            torch.cuda.synchronize()
+        outs.append((out.detach(), pt.grad, wit))
+    (o0, g0, w0), (o1, g1, w1) = outs
+    assert w0["npf_mean_agg_fwd"] == 1 and w0["npf_mean_agg_bwd"] == 1 and w0["npf_masked_mean_fwd"] == 0, w0
+    assert w1["npf_masked_mean_fwd"] == 1 and w1["npf_masked_mean_bwd"] == 1 and w1["npf_mean_agg_fwd"] == 0, w1
+    assert torch.equal(o1, o0) and torch.equal(g1, g0)
+    assert float(o0.abs().max()) > 0 and float(g0.abs().max()) > 0  # (not two tensors of zeros)
+
+
 def test_masked_exports_refuse_bad_sizes():
     from npf_gwwaveform_amd import _lib as L
     from npf_gwwaveform_amd import chain as CH

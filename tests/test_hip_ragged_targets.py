@@ -113,21 +113,26 @@ def test_masked_head_matches_float64(dy, homosk, n_z, T_pad):
                 assert float(slp[r].detach()) == 0.0
 
 
+@pytest.mark.parametrize("rows,T,dy", ((6, 300, 2), (2, 1, 1), (4, 257, 16)))
 @pytest.mark.parametrize("homosk", (False, True))
-def test_masked_head_at_full_counts_is_the_unmasked_head_bit_for_bit(homosk):
-    """Counts at and above T (clamped) against ``npf_gauss_head_fwd`` / ``_bwd``: the same loops in the same order."""
+def test_masked_head_at_full_counts_is_the_unmasked_head_bit_for_bit(homosk, rows, T, dy):
+    """Counts at and above T (clamped) against ``npf_gauss_head_fwd`` / ``_bwd``: the same loops in the same order.  T = 1: a single
+    point, 255 idle threads in every reduction; 257 * 16 elements: more than one stride of the element loop at the widest dy.
+    ``want_dist=False``: the backward pass recomputes loc / scale (and the pooled scale) from ``suff``."""
     from npf_gwwaveform_amd import functional as FN
 
     g = torch.Generator().manual_seed(5)
-    suff, Y = torch.randn(6, 300, 4, generator=g).to(DEV), torch.randn(2, 300, 2, generator=g).to(DEV)
-    outs = []
-    for n_valid in (None, torch.tensor([300, 10 ** 6], device=DEV)):
-        s = suff.clone().requires_grad_(True)
-        loc, scale, slp = FN.gauss_head(s, Y, 2, homosk, n_valid=n_valid)
-        (slp.sum() + (loc * scale).sum()).backward()
-        outs.append((loc, scale, slp, s.grad))
-    for a, b in zip(*outs):
-        assert torch.equal(a, b)
+    suff, Y = torch.randn(rows, T, 2 * dy, generator=g).to(DEV), torch.randn(2, T, dy, generator=g).to(DEV)
+    for want_dist in (True, False):
+        outs = []
+        for n_valid in (None, torch.tensor([T, 10 ** 6], device=DEV)):
+            s = suff.clone().requires_grad_(True)
+            loc, scale, slp = FN.gauss_head(s, Y, dy, homosk, want_dist=want_dist, n_valid=n_valid)
+            (slp.sum() + (loc * scale).sum()).backward()
+            outs.append((loc, scale, slp, s.grad))
+        for a, b in zip(*outs):
+            assert torch.equal(a, b), f"want_dist={want_dist}"
+        assert (loc.numel() > 0) == want_dist and float(s.grad.abs().max()) > 0
 
 
 # ---- 2. attention with query counts --------------------------------------------------------------------------------------------
