@@ -523,6 +523,21 @@ int npf_masked_attn_fwd_nq(const float *q, const float *k, const float *v, const
 int npf_masked_attn_bwd_nq(const float *q, const float *k, const float *v, const int32_t *n_valid, const int32_t *n_q_valid,
                            const float *out, const float *d_out, const float *lse, int32_t n_tasks, int32_t n_keys, int32_t n_queries,
                            int32_t d, float scale, float *d_q, float *d_k, float *d_v, void *stream);
+/* A shared prefix and an own tail (inference only, no backward): n_tasks = S * n_prefix_tasks tasks, task j attends over the first
+ * n_prefix[j % n_prefix_tasks] rows of PREFIX task j % n_prefix_tasks (k_pre / v_pre: PT32 [n_prefix_tasks][c_pad][d]) followed by the
+ * first n_tail[j] rows of its own tail (k_tail / v_tail: PT32 [n_tasks][m_tail][d]):
+ *   out(j, q, :) = softmax(scale <Q(j,q,:), [K_pre(j % P, :n_prefix); K_tail(j, :n_tail)]>) [V_pre; V_tail],   0 if both counts are 0.
+ * S function samples of one conditioned context read it from one copy.  n_prefix [n_prefix_tasks] / n_tail [n_tasks]: DEVICE int32,
+ * clamped to [0, c_pad] / [0, m_tail], never read by the host.  n_q_valid [n_tasks]: as in npf_masked_attn_fwd_nq, or NULL.  The key
+ * blocks of the prefix are walked first, then those of the tail, each segment ending as the single one of npf_masked_attn_fwd does;
+ * with every n_tail == 0 and S == 1 the result is bit-identical to npf_masked_attn_fwd on the prefix.  With heads as extra tasks the
+ * caller orders them sample-major (task s * (B H) + h * B + b over a prefix split by npf_split_heads).  Every element of out (whole
+ * tiles) is written.  Status: NPF_EINVAL (nothing launched) for d % 4 != 0, d > 256, n_prefix_tasks <= 0, n_tasks % n_prefix_tasks != 0
+ * or a negative size. */
+int npf_masked_attn_fwd_prefix(const float *q, const float *k_pre, const float *v_pre, const int32_t *n_prefix, const float *k_tail,
+                               const float *v_tail, const int32_t *n_tail, const int32_t *n_q_valid, int32_t n_tasks,
+                               int32_t n_prefix_tasks, int32_t c_pad, int32_t m_tail, int32_t n_queries, int32_t d, float scale,
+                               float *out, void *stream);
 /* out[task][F] (row-major) = mean over the first n_valid[task] points of PT32 tensor R (F % 32 == 0), zeros if n_valid[task] == 0
  * (torch.mean(R_cntxt, dim=1) on the batch cut per task, np.py:95, attnnp.py:181); tiles beyond the count are not read. */
 int npf_masked_mean_fwd(const float *R_pt, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *out,

@@ -397,6 +397,37 @@ def _no_bf16_masked():
         raise NotImplementedError("per-task context counts (n_valid / n_cntxt) are not implemented in the bf16 compute mode")
 
 
+class PrefixTail:
+    """The keys / values of ``n_tasks = S * n_prefix_tasks`` tasks as two segments (``functional.masked_attention_prefix``): a prefix
+    shared by the S tasks ``j, j + n_prefix_tasks, ...`` (``k_pre`` / ``v_pre`` PT32 [n_prefix_tasks, c_pad, .], counts ``n_pre``) and a
+    tail of every task's own (``k_tail`` / ``v_tail`` PT32 [n_tasks, m_tail, .], counts ``n_tail``).  Handed to ``attend_pt`` in the
+    place of ``n_valid``.  For an attender with learned projections the tensors hold the PROJECTED keys / values: the prefix already
+    split into heads (``heads_of_prefix`` > 0: prefix task ``h * B + b``), the tails not yet."""
+
+    def __init__(self, k_pre, v_pre, n_pre, k_tail, v_tail, n_tail, n_prefix_tasks, c_pad, m_tail, heads_of_prefix=0):
+        self.k_pre, self.v_pre, self.n_pre, self.k_tail, self.v_tail, self.n_tail = k_pre, v_pre, n_pre, k_tail, v_tail, n_tail
+        self.n_prefix_tasks, self.c_pad, self.m_tail, self.heads_of_prefix = n_prefix_tasks, c_pad, m_tail, heads_of_prefix
+
+    def live(self, n_tasks):
+        """bool [n_tasks]: does the task have a key in either segment (``n_tasks`` = S * the tasks the counts were given for)."""
+        B = self.n_pre.shape[0]
+        return ((self.n_pre.clamp(0, self.c_pad).repeat(n_tasks // B) + self.n_tail.clamp(0, self.m_tail)) > 0)
+
+
+def _sample_major(x, S, H, B):
+    """Tasks [H, S, B] (``npf_split_heads`` of S x B tasks: task ``h * S B + s * B + b``) -> [S, H, B] (task ``s * B H + h * B + b``, so
+    that the kernel's ``j % (B H)`` is ``h * B + b``, the index ``npf_split_heads`` gives head ``h`` of task ``b`` of the prefix), one
+    copy on the device."""
+    rest = x.shape[1:]
+    return x.view(H, S, B, *rest).transpose(0, 1).contiguous().view(S * H * B, *rest)
+
+
+def _head_major(x, S, H, B):
+    """Inverse of ``_sample_major``."""
+    rest = x.shape[1:]
+    return x.view(S, H, B, *rest).transpose(0, 1).contiguous().view(H * S * B, *rest)
+
+
 class DotAttender(nn.Module):
     """Scaled dot-product cross attention without learned projections:
     ``softmax(Q K^T / sqrt(d)) V`` (npf/architectures/attention.py:89-220)."""
@@ -434,6 +465,11 @@ class DotAttender(nn.Module):
 
         if n_q_valid is not None and n_valid is None:
             raise NotImplementedError("n_q_valid needs n_valid: query counts are an option of the masked attention kernel")
+        if isinstance(n_valid, PrefixTail):  # (a shared prefix and an own tail per task: Conditioned.sample_functions)
+            _no_bf16_masked()
+            w, scale = n_valid, 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
+            return FN.masked_attention_prefix(queries_pt, w.k_pre, w.v_pre, w.n_pre, w.k_tail, w.v_tail, w.n_tail, queries_pt.shape[0],
+                                              w.n_prefix_tasks, w.c_pad, w.m_tail, n_queries, self.kq_size, scale, n_q_valid=n_q_valid)
         if n_valid is not None:
             _no_bf16_masked()
             scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
@@ -521,6 +557,22 @@ class MultiheadAttender(nn.Module):
         H, d = self.n_heads, self.kq_size
         if n_q_valid is not None and n_valid is None:
             raise NotImplementedError("n_q_valid needs n_valid: query counts are an option of the masked attention kernel")
+        if isinstance(n_valid, PrefixTail):
+            # heads as tasks over two segments: the prefix was projected and split once (prefix task h * B0 + b), the projected tails
+            # are split here; queries, tails and counts go sample-major (task s * (B0 H) + h * B0 + b) so that the kernel's
+            # j % (B0 H) is the prefix task
+            _no_bf16_masked()
+            w = n_valid
+            if n_q_valid is not None or w.heads_of_prefix != H:
+                raise NotImplementedError("a prefix / tail context with learned projections: no query counts, the prefix split into this attender's heads")
+            B0 = w.n_prefix_tasks // H
+            S = B // B0
+            Qp = queries_proj if queries_proj is not None else self._project(queries_pt, B, T, self.query_transform)
+            Qh, Kt, Vt = (_sample_major(FN.split_heads(x, B, n, d, H), S, H, B0) for x, n in ((Qp, T), (w.k_tail, w.m_tail), (w.v_tail, w.m_tail)))
+            n_tail = FN.counts_i32(w.n_tail, B, "n_tail").view(S, 1, B0).expand(S, H, B0).reshape(S * H * B0)
+            heads = PrefixTail(w.k_pre, w.v_pre, FN.counts_i32(w.n_pre, B0, "n_pre").repeat(H), Kt, Vt, n_tail, H * B0, w.c_pad, w.m_tail)
+            Oh = self.dot.attend_pt(Qh, None, None, C, T, n_valid=heads)
+            return FN.merge_heads(_head_major(Oh, S, H, B0), B, T, self.value_size, H)
         if n_valid is not None:
             _no_bf16_masked()
             Kh = FN.split_heads(self._project(keys_pt, B, C, self.key_transform), B, C, d, H)

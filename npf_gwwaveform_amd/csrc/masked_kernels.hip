@@ -21,6 +21,12 @@
 // returns before it stages a key block; inside the boundary block the queries beyond the count are not live; the d_k / d_v walk over
 // the queries ends at the count, so Q / O / dO / lse rows beyond it are never read.  Block order and summation order are those of
 // the instances without a query count: the rows below the counts come out bit-identical.
+//
+// A shared prefix and an own tail (npf_masked_attn_fwd_prefix, the PFX instances of the forward kernel, inference only): task j walks
+// the key blocks of PREFIX task j % n_pre_tasks up to its count and then those of its own tail up to n_tail[j] -- S function samples
+// of one conditioned context read the context's keys / values from one copy and keep only the rows they drew themselves.  Each
+// segment ends as the single one does (blocks beyond the count skipped, the last block's rows beyond it zeros / -inf); the running
+// maximum, sum and accumulator carry over the switch.  With every tail count 0 the block sequence is that of npf_masked_attn_fwd.
 #include "npf_common.hpp"
 
 namespace npf {
@@ -65,13 +71,34 @@ struct MkGeom {
   static constexpr int LDA = DP + 2, LDB = DP + 4;
 };
 
+// The second key segment of the PFX instances of the forward kernel; without PFX an empty argument
+template <bool PFX>
+struct MkTail {
+  const float* K2;
+  const float* V2;
+  const int32_t* n_valid2;
+  int n_keys2, n_pre_tasks;
+  __device__ __forceinline__ int prefix_task(int b) const { return b % n_pre_tasks; }
+  __device__ __forceinline__ int tail_count(int b) const { return clamp_count(n_valid2, b, n_keys2); }
+};
+template <>
+struct MkTail<false> {
+  static constexpr const float* K2 = nullptr;
+  static constexpr const float* V2 = nullptr;
+  static constexpr int n_keys2 = 0;
+  __device__ __forceinline__ int prefix_task(int b) const { return b; }
+  __device__ __forceinline__ int tail_count(int) const { return 0; }
+};
+
 // One workgroup = one task and 64 queries (16 per wave); DP = the tile width the instance computes on (d <= DP).
 // NQ: the task's queries beyond n_q_valid[b] are padding (zeros out, never read); without it n_q_valid is not looked at.
-template <int DP, bool NQ>
-__global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K,
-                                                             const float* __restrict__ V, const int32_t* __restrict__ n_valid,
-                                                             const int32_t* __restrict__ n_q_valid, float* __restrict__ O,
-                                                             float* __restrict__ lse, int n_keys, int T, int Fp, int d, float scale) {
+// PFX: K / V / n_valid / n_keys are those of prefix task b % tl.n_pre_tasks, walked first; tl holds the task's own tail, walked second.
+template <int DP, bool NQ, bool PFX>
+__device__ __forceinline__ void masked_attn_fwd_body(const float* __restrict__ Q, const float* __restrict__ K,
+                                                     const float* __restrict__ V, const int32_t* __restrict__ n_valid,
+                                                     const int32_t* __restrict__ n_q_valid, float* __restrict__ O,
+                                                     float* __restrict__ lse, int n_keys, int T, int Fp, int d, float scale,
+                                                     const MkTail<PFX> tl) {
   using G = MkGeom<DP>;
   constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
   __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
@@ -80,8 +107,10 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
   const int c = lane & 15, g = lane >> 4;
   const int qblocks = (T + 63) >> 6;
   const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
-  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
-  const int nv = clamp_count(n_valid, b, n_keys);
+  const int tilesC0 = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int bp = tl.prefix_task(b);
+  const int nv0 = clamp_count(n_valid, bp, n_keys);
+  const int nv1 = tl.tail_count(b);  // (both uniform over the workgroup)
   const int nq = NQ ? clamp_count(n_q_valid, b, T) : T;
   const int q = qb * 64 + wave * 16 + c;
   if (NQ && qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zeros, no key staged
@@ -101,46 +130,55 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
-  for (int key0 = 0; key0 < nv; key0 += KB) {  // (nv is uniform over the workgroup)
-    __syncthreads();
-    mk_stage<DP, KB, LDK>(K, b, tilesC, Fp, d, key0, nv, Ks, tid);
-    mk_stage<DP, KB, LDV>(V, b, tilesC, Fp, d, key0, nv, Vs, tid);
-    __syncthreads();
-    f32x4 S[NSB];  // S^T[key = key0 + 16 sb + 4 g + i][q = c]
-    float bm = -INFINITY;
+#pragma unroll 1
+  for (int seg = 0; seg < (PFX ? 2 : 1); ++seg) {  // (one segment without PFX: the loop is gone)
+    const bool tail = PFX && seg == 1;
+    const float* __restrict__ Kg = tail ? tl.K2 : K;
+    const float* __restrict__ Vg = tail ? tl.V2 : V;
+    const int tilesC = tail ? (tl.n_keys2 + 31) >> 5 : tilesC0;
+    const int bk = tail ? b : bp;  // the task whose rows the segment reads
+    const int nv = tail ? nv1 : nv0;
+    for (int key0 = 0; key0 < nv; key0 += KB) {
+      __syncthreads();
+      mk_stage<DP, KB, LDK>(Kg, bk, tilesC, Fp, d, key0, nv, Ks, tid);
+      mk_stage<DP, KB, LDV>(Vg, bk, tilesC, Fp, d, key0, nv, Vs, tid);
+      __syncthreads();
+      f32x4 S[NSB];  // S^T[key = key0 + 16 sb + 4 g + i][q = c]
+      float bm = -INFINITY;
 #pragma unroll
-    for (int sb = 0; sb < NSB; ++sb) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      for (int sb = 0; sb < NSB; ++sb) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kc = 0; kc < NKC; ++kc) acc = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], acc);
+        for (int kc = 0; kc < NKC; ++kc) acc = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], acc);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        acc[i] = (key0 + 16 * sb + 4 * g + i < nv) ? acc[i] * scale : -INFINITY;
-        bm = fmaxf(bm, acc[i]);
+        for (int i = 0; i < 4; ++i) {
+          acc[i] = (key0 + 16 * sb + 4 * g + i < nv) ? acc[i] * scale : -INFINITY;
+          bm = fmaxf(bm, acc[i]);
+        }
+        S[sb] = acc;
       }
-      S[sb] = acc;
+      // (key0 < nv: the block has a real key, so its maximum is finite)
+      const float m_new = fmaxf(m, mk_max4(bm));
+      const float alpha = expf(m - m_new);  // (0 at the first block: m = -inf)
+      float ps = 0.f;
+#pragma unroll
+      for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          S[sb][i] = expf(S[sb][i] - m_new);  // (exp(-inf) = 0 beyond the count)
+          ps += S[sb][i];
+        }
+      l = l * alpha + mk_sum4(ps);
+      m = m_new;
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
+#pragma unroll
+      for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) o[dt] = mk_mfma(Vs[(16 * sb + 4 * g + j) * LDV + 16 * dt + c], S[sb][j], o[dt]);
     }
-    // (key0 < nv: the block has a real key, so its maximum is finite)
-    const float m_new = fmaxf(m, mk_max4(bm));
-    const float alpha = expf(m - m_new);  // (0 at the first block: m = -inf)
-    float ps = 0.f;
-#pragma unroll
-    for (int sb = 0; sb < NSB; ++sb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        S[sb][i] = expf(S[sb][i] - m_new);  // (exp(-inf) = 0 beyond the count)
-        ps += S[sb][i];
-      }
-    l = l * alpha + mk_sum4(ps);
-    m = m_new;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
-#pragma unroll
-    for (int sb = 0; sb < NSB; ++sb)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) o[dt] = mk_mfma(Vs[(16 * sb + 4 * g + j) * LDV + 16 * dt + c], S[sb][j], o[dt]);
   }
   const float inv = (live && l > 0.f) ? 1.f / l : 0.f;  // (no real key: zeros; the tile's rows beyond T: zeros)
   if (q < tilesT * 32) {
@@ -148,8 +186,26 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
     for (int dt = 0; dt < NDT; ++dt)
       if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = o[dt] * inv;
   }
-  if (live && g == 0 && lse != nullptr) lse[(size_t)b * T + q] = nv > 0 ? m + logf(l) : 0.f;
+  if (live && g == 0 && lse != nullptr) lse[(size_t)b * T + q] = nv0 + nv1 > 0 ? m + logf(l) : 0.f;
   if (NQ && !live && q < T && g == 0 && lse != nullptr) lse[(size_t)b * T + q] = 0.f;
+}
+
+// (the two entries of the one body: the PFX flag changes the arguments, so the instances without it keep theirs)
+template <int DP, bool NQ>
+__global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                             const float* __restrict__ V, const int32_t* __restrict__ n_valid,
+                                                             const int32_t* __restrict__ n_q_valid, float* __restrict__ O,
+                                                             float* __restrict__ lse, int n_keys, int T, int Fp, int d, float scale) {
+  masked_attn_fwd_body<DP, NQ, false>(Q, K, V, n_valid, n_q_valid, O, lse, n_keys, T, Fp, d, scale, MkTail<false>{});
+}
+
+template <int DP, bool NQ>
+__global__ __launch_bounds__(256) void masked_attn_fwd_prefix_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                    const float* __restrict__ V, const int32_t* __restrict__ n_valid,
+                                                                    const int32_t* __restrict__ n_q_valid, float* __restrict__ O,
+                                                                    int n_keys, int T, int Fp, int d, float scale,
+                                                                    const MkTail<true> tl) {
+  masked_attn_fwd_body<DP, NQ, true>(Q, K, V, n_valid, n_q_valid, O, nullptr, n_keys, T, Fp, d, scale, tl);
 }
 
 // d_q: the forward pass's geometry.  dS^T = scale P^T (dP^T - D), P from the log-sum-exp, D[q] = <dO[q], O[q]>.
@@ -439,6 +495,34 @@ extern "C" int npf_masked_attn_fwd_nq(const float* q, const float* k, const floa
                                       float scale, float* out, float* lse, void* stream) {
   if (!n_q_valid) return NPF_EINVAL;
   return masked_attn_fwd(q, k, v, n_valid, n_q_valid, n_tasks, n_keys, n_queries, d, scale, out, lse, stream);
+}
+
+extern "C" int npf_masked_attn_fwd_prefix(const float* q, const float* k_pre, const float* v_pre, const int32_t* n_prefix,
+                                          const float* k_tail, const float* v_tail, const int32_t* n_tail, const int32_t* n_q_valid,
+                                          int32_t n_tasks, int32_t n_prefix_tasks, int32_t c_pad, int32_t m_tail, int32_t n_queries,
+                                          int32_t d, float scale, float* out, void* stream) {
+  if (n_tasks < 0 || n_prefix_tasks <= 0 || n_tasks % n_prefix_tasks != 0 || c_pad < 0 || m_tail < 0 || n_queries < 0) return NPF_EINVAL;
+  if (d <= 0 || (d & 3) || d > 256) return NPF_EINVAL;
+  if (!q || !out || !n_prefix || !n_tail || (c_pad > 0 && (!k_pre || !v_pre)) || (m_tail > 0 && (!k_tail || !v_tail))) return NPF_EINVAL;
+  if (mk_misaligned(q, k_pre, v_pre, out) || mk_misaligned(k_tail, v_tail)) return NPF_EINVAL;
+  if (n_tasks == 0 || n_queries == 0) return NPF_OK;
+  const int Fp = npf::round_up(d, 32);
+  const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define MK_PFX_I(DP, NQ)                                                                                                         \
+  hipLaunchKernelGGL((npf::masked_attn_fwd_prefix_kernel<DP, NQ>), grid, block, 0, st, q, k_pre, v_pre, n_prefix, n_q_valid, out, \
+                     c_pad, n_queries, Fp, d, scale, npf::MkTail<true>{k_tail, v_tail, n_tail, m_tail, n_prefix_tasks})
+#define MK_PFX(DP) MK_PFX_I(DP, false)
+#define MK_PFX_NQ(DP) MK_PFX_I(DP, true)
+  if (n_q_valid)
+    MK_DISPATCH(MK_PFX_NQ);
+  else
+    MK_DISPATCH(MK_PFX);
+#undef MK_PFX_NQ
+#undef MK_PFX
+#undef MK_PFX_I
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
 }
 
 extern "C" int npf_masked_attn_bwd_nq(const float* q, const float* k, const float* v, const int32_t* n_valid,

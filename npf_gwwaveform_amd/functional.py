@@ -525,6 +525,43 @@ def masked_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor,
     return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale, n_q_valid)
 
 
+def masked_attention_prefix(q_pt: torch.Tensor, k_pre: torch.Tensor, v_pre: torch.Tensor, n_prefix: torch.Tensor, k_tail: torch.Tensor,
+                            v_tail: torch.Tensor, n_tail: torch.Tensor, n_tasks: int, n_prefix_tasks: int, c_pad: int, m_tail: int,
+                            n_queries: int, d: int, scale: float, n_q_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PT32 [n_tasks, n_queries, d]: scaled-dot attention of task ``j`` over the first ``n_prefix[j % n_prefix_tasks]`` rows of PREFIX
+    task ``j % n_prefix_tasks`` (``k_pre`` / ``v_pre``: PT32 [n_prefix_tasks, c_pad, d], shared by the ``n_tasks / n_prefix_tasks``
+    tasks that map to it) followed by the first ``n_tail[j]`` rows of its own tail (``k_tail`` / ``v_tail``: PT32 [n_tasks, m_tail, d]);
+    zeros where both counts are 0 (``npf_masked_attn_fwd_prefix``).  Counts and ``n_q_valid`` as in :func:`masked_attention`: device
+    int32 / int64, read by the kernel only.  Inference only -- there is no backward pass, and a call in which an input requires grad
+    is refused."""
+    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
+        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
+    if n_prefix_tasks < 1 or n_tasks < 0 or n_tasks % n_prefix_tasks != 0:
+        raise ValueError(f"n_tasks={n_tasks} must be a multiple of n_prefix_tasks={n_prefix_tasks} >= 1 (task j reads prefix j % n_prefix_tasks)")
+    if c_pad < 0 or m_tail < 0 or n_queries < 0:
+        raise ValueError(f"negative size: c_pad={c_pad}, m_tail={m_tail}, n_queries={n_queries}")
+    tensors = (q_pt, k_pre, v_pre, k_tail, v_tail)
+    if any(t.requires_grad for t in tensors):
+        raise RuntimeError("masked_attention_prefix is inference only (no backward pass): detach the inputs")
+    from .chain import pt_shape
+
+    for what, t, shape in (("q_pt", q_pt, pt_shape(n_tasks, n_queries, d)), ("k_pre", k_pre, pt_shape(n_prefix_tasks, c_pad, d)),
+                           ("v_pre", v_pre, pt_shape(n_prefix_tasks, c_pad, d)), ("k_tail", k_tail, pt_shape(n_tasks, m_tail, d)),
+                           ("v_tail", v_tail, pt_shape(n_tasks, m_tail, d))):
+        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
+            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    n_prefix, n_tail = counts_i32(n_prefix, n_prefix_tasks, "n_prefix"), counts_i32(n_tail, n_tasks, "n_tail")
+    if n_q_valid is not None:
+        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
+    q_pt, k_pre, v_pre, k_tail, v_tail = (t.detach().contiguous() for t in tensors)
+    out = torch.empty(pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
+    L.check(L.load().npf_masked_attn_fwd_prefix(L.ptr(q_pt), L.ptr(k_pre), L.ptr(v_pre), _iptr(n_prefix), L.ptr(k_tail), L.ptr(v_tail),
+                                                _iptr(n_tail), _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks,
+                                                n_prefix_tasks, c_pad, m_tail, n_queries, d, float(scale), L.ptr(out), L.stream_ptr()),
+            "npf_masked_attn_fwd_prefix")
+    return out
+
+
 def masked_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
     """Mean over the first ``n_valid[task]`` points of a PT32 tensor -> row-major [n_tasks, pad32(F)] (zeros where a task has none):
     ``torch.mean(R, dim=1)`` (npf/neuralproc/np.py:95, attnnp.py:181) of the batch cut per task; counts as in :func:`masked_attention`."""

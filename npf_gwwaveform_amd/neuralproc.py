@@ -26,7 +26,7 @@ import torch.nn as nn
 from torch.distributions import Independent, Normal
 
 from . import functional as FN
-from .architectures import (MLP, DotAttender, MergeFlatInputs, MultiheadAttender, SelfAttention, get_attender,
+from .architectures import (MLP, DotAttender, MergeFlatInputs, MultiheadAttender, PrefixTail, SelfAttention, get_attender,
                             merge_flat_input)
 from .chain import Chain, PTensor, pad32, pt_shape
 
@@ -214,6 +214,166 @@ class Conditioned:
             Y[:, s:s + chunk] = y
             self.extend(x, y)
         return Y
+
+    def _function_sampler(self, X_trgt, n_samples, eps, chunk):
+        """The argument checks of :meth:`sample_functions` -> (its per-call state, ``eps``, ``chunk``)."""
+        m = self._model
+        m._refuse_unimplemented("sample_functions")
+        if self.z_samples is not None and self.z_samples.shape[0] != 1:
+            raise ValueError(f"sample_functions draws one trajectory per sample: condition with n_z_samples=1 (got {self.z_samples.shape[0]})")
+        if X_trgt.dim() != 3 or X_trgt.shape[0] != self.B or X_trgt.shape[2] != m.x_dim:
+            raise ValueError(f"X_trgt must be [B={self.B}, T, x_dim={m.x_dim}], got {list(X_trgt.shape)}")
+        T = X_trgt.shape[1]
+        if T == 0:
+            raise ValueError("X_trgt holds no target points")
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError(f"n_samples must be at least 1, got {n_samples}")
+        if eps is not None and tuple(eps.shape) != (S, self.B, T, m.y_dim):
+            raise ValueError(f"eps must be [S={S}, B={self.B}, T={T}, y_dim={m.y_dim}], got {list(eps.shape)}")
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be at least 1, got {chunk}")
+        padded_kind = self.capacity is not None or (self.n_cntxt is not None and self.C > 0)
+        if self._fused_t and not padded_kind:
+            raise ValueError("sample_functions: this context was stored for the fused target side (images of keys / values only); "
+                             "condition with counts (n_cntxt=...) or a capacity (condition_with_capacity)")
+        m._check_tensors(X_trgt, eps)
+        if eps is None:
+            eps = torch.randn(S, self.B, T, m.y_dim, device=X_trgt.device)
+        with torch.no_grad():
+            return _FunctionSampler(self, S, T, X_trgt.device), eps, chunk
+
+    def sample_functions(self, X_trgt, n_samples, eps=None, chunk=1) -> torch.Tensor:
+        """``n_samples`` coherent function draws per task at ``X_trgt`` [B, T, x_dim] -> ``Y`` [S, B, T, y_dim]: sample ``s`` of task ``b``
+        is what :meth:`rollout` returns for task ``b`` of a batch tiled S times, run with ``eps[s]`` (``eps`` [S, B, T, y_dim] standard
+        normal, default one ``torch.randn`` draw; ``chunk`` as in ``rollout``).  The conditioned state is READ ONLY and stored once:
+        the S x B trajectories (task ``s * B + b``) attend over / pool the shared context rows followed by a scratch tail of the points
+        they drew themselves (T rows rounded up to whole tiles, owned by this call; ``npf_masked_attn_fwd_prefix``), so a later
+        ``query`` / ``rollout`` / ``sample_functions`` sees the state as it was.  A latent model needs ``n_z == 1``; every sample
+        recomputes q(z | C + its draws) with the state's ``eps``.  Accepts a state conditioned with a capacity, with ``n_cntxt``, or
+        without counts if it was not stored for the fused target side.  Inference only, no host sync."""
+        sampler, eps, chunk = self._function_sampler(X_trgt, n_samples, eps, chunk)
+        S, B, T = sampler.S, self.B, X_trgt.shape[1]
+        m = self._model
+        Y = torch.empty(S, B, T, m.y_dim, device=X_trgt.device)
+        with torch.no_grad():
+            for t0 in range(0, T, chunk):
+                x = X_trgt[:, t0:t0 + chunk]
+                n = x.shape[1]
+                x = x.unsqueeze(0).expand(S, B, n, m.x_dim).reshape(S * B, n, m.x_dim)
+                y = sampler.step(x, eps[:, :, t0:t0 + chunk].reshape(S * B, n, m.y_dim))
+                Y[:, :, t0:t0 + chunk] = y.view(S, B, n, m.y_dim)
+        return Y
+
+
+def tail_capacity(T: int) -> int:
+    """Rows per task of the scratch tails of ``sample_functions``: the T drawn points rounded up to whole 32-point tiles."""
+    return pad32(T)
+
+
+def pooled_mean_of_two(mean_p, n_p, mean_t, n_t):
+    """Mean over the union of two row sets from their means and sizes: ``(n_p mean_p + n_t mean_t) / max(n_p + n_t, 1)`` -- zeros where
+    both are empty.  ``mean_*`` [..., r] float, ``n_*`` [...] integer (or float) counts, broadcast over the features."""
+    n_p, n_t = n_p.to(mean_p.dtype).unsqueeze(-1), n_t.to(mean_t.dtype).unsqueeze(-1)
+    return (n_p * mean_p + n_t * mean_t) / (n_p + n_t).clamp(min=1)
+
+
+class _FunctionSampler:
+    """The state of one ``Conditioned.sample_functions`` call: S x B tasks in sample-major order (task ``j = s * B + b`` reads prefix
+    task ``j % B``) whose context is the conditioned state -- read only, stored once -- followed by a scratch tail of the points the
+    task drew itself.  :meth:`step` is one autoregressive step (query a block, draw, append) without host sync or a change of any
+    tensor's storage, so it can be captured in a graph and replayed block after block."""
+
+    def __init__(self, post: "Conditioned", S: int, T: int, device):
+        m = post._model
+        self.post, self.m, self.S, self.B, self.SB = post, m, S, post.B, S * post.B
+        B, r = post.B, m.r_dim
+        self.c_pad = post.C if post.capacity is None else post.capacity
+        self.m_tail = tail_capacity(T)
+        if post.n_cntxt is not None:
+            self.n_pre = post.n_cntxt  # (the live device counts: read by the kernels at every step)
+        else:  # (conditioned without counts: every task holds all C rows)
+            self.n_pre = torch.full((B,), self.c_pad, dtype=torch.int32, device=device)
+        self.n_tail = torch.zeros(self.SB, dtype=torch.int32, device=device)
+        zeros = lambda n, pts, F: torch.zeros(pt_shape(n, pts, F), device=device)  # noqa: E731
+        att = getattr(m, "attender", None)
+        latent = post.z_samples is not None
+        # the tails ``npf_append_points`` fills, as (tensor, features): the per-point representations of the drawn points (the values
+        # of scaled-dot attention, what CNP / LNP and the latent path of AttnLNP pool), then the attention's keys [and values]
+        self.keep_R = not m._attentive or isinstance(att, DotAttender) or latent
+        self.R_tail = zeros(self.SB, self.m_tail, r) if self.keep_R else None
+        self.tails = [(self.R_tail, r)] if self.keep_R else []
+        if m._attentive:
+            Xc = post._Xc_pt.t if post._Xc_pt is not None else zeros(B, 0, m.x_transf_dim)
+            R = post._R.t if post._R is not None else zeros(B, 0, r)
+            if isinstance(att, DotAttender):
+                self.K_tail = zeros(self.SB, self.m_tail, m.x_transf_dim)
+                self.tails.append((self.K_tail, m.x_transf_dim))
+                self.walk = PrefixTail(Xc, R, self.n_pre, self.K_tail, self.R_tail, self.n_tail, B, self.c_pad, self.m_tail)
+            else:  # learned projections: the prefix projected and split into heads once, the tails hold projected rows
+                H, d = att.n_heads, att.kq_size
+                if self.c_pad > 0:
+                    Kh = FN.split_heads(att._project(Xc, B, self.c_pad, att.key_transform), B, self.c_pad, d, H)
+                    Vh = FN.split_heads(att._project(R, B, self.c_pad, att.value_transform), B, self.c_pad, att.value_size, H)
+                else:  # (conditioned on no context at all: an empty prefix, nothing to project)
+                    Kh, Vh = zeros(H * B, 0, d // H), zeros(H * B, 0, att.value_size // H)
+                self.K_tail, self.V_tail = zeros(self.SB, self.m_tail, d), zeros(self.SB, self.m_tail, att.value_size)
+                self.tails += [(self.K_tail, d), (self.V_tail, att.value_size)]
+                self.walk = PrefixTail(Kh, Vh, self.n_pre, self.K_tail, self.V_tail, self.n_tail, H * B, self.c_pad, self.m_tail,
+                                       heads_of_prefix=H)
+            # the pooled prefix representation of the latent path (AttnLNP)
+            self.mean_pre = FN.masked_mean(R, self.n_pre, B, self.c_pad, r)[:, :r] if (latent and self.c_pad > 0) \
+                else torch.zeros(B, r, device=device)
+        else:
+            self.walk = None
+            self.mean_pre = post._R.reshape(B, r)  # (CNP / LNP keep the pooled mean of the context)
+        self.eps_z = None
+        if latent:
+            if post.eps is not None:
+                eps = post.eps
+            else:  # (``condition`` keeps z, not the draw behind it: the same draw, from z = loc + scale * eps)
+                q = post.q_zCc.base_dist
+                eps = (post.z_samples - q.loc) / q.scale
+            self.eps_z = eps[0].repeat(S, 1, 1)  # [S B, 1, z]: every sample of task b is drawn with the state's eps of task b
+
+    def _pooled(self):
+        """[S B, 1, r]: the mean representation over each task's prefix and tail rows."""
+        m, r = self.m, self.m.r_dim
+        mean_t = FN.masked_mean(self.R_tail, self.n_tail, self.SB, self.m_tail, r)[:, :r]
+        n_p = self.n_pre.clamp(0, self.c_pad).repeat(self.S)
+        return pooled_mean_of_two(self.mean_pre.repeat(self.S, 1), n_p, mean_t, self.n_tail).reshape(self.SB, 1, r)
+
+    def step(self, x, eps):
+        """``x`` [S B, n, x_dim], ``eps`` [S B, n, y_dim] -> ``y`` [S B, n, y_dim] drawn given each task's context and earlier draws;
+        the tails grow by the n points."""
+        m, SB = self.m, self.SB
+        n = x.shape[1]
+        Xt_pt = m._xenc_pt(x)
+        z = None
+        R = None
+        if self.eps_z is not None or not m._attentive:
+            R = self._pooled()
+        if self.eps_z is not None:
+            q = m._latent_dist_from(R).base_dist
+            z = (q.loc + q.scale * self.eps_z).unsqueeze(0)  # [1, S B, 1, z]
+        C = self.c_pad + self.m_tail
+        if m._attentive:
+            suff = m._target_suffstat(None, z, None, Xt_pt, SB, C, n, n_valid=self.walk)
+        else:
+            suff = m._target_suffstat(None, z, R, Xt_pt, SB, C, n)
+        p = m._head(suff, None, SB, n).base_dist
+        y = p.loc[0] + p.scale[0] * eps
+        Xn_pt, Rn_pts = m._encode_points(x, y)
+        src = [Rn_pts.t] if self.keep_R else []
+        if m._attentive:
+            att = m.attender
+            if isinstance(att, DotAttender):
+                src.append(Xn_pt.t)
+            else:
+                src += [att._project(Xn_pt.t, SB, n, att.key_transform), att._project(Rn_pts.t, SB, n, att.value_transform)]
+        FN.append_points([(s, dst, F) for s, (dst, F) in zip(src, self.tails)], self.n_tail, None, SB, n, self.m_tail)
+        return y
 
 
 def _mean_rows(R_pt, pts, B, r, n_valid=None):
@@ -855,9 +1015,14 @@ class AttnCNP(NeuralProcessFamily):
         on the batch cut per task).  A task without context gets zeros, as ``trgt_dependent_representation`` at C = 0 -- also
         behind an attender whose learned layers would turn zero context vectors into something else.  ``n_q_valid``: the target
         sizes of a batch whose targets are padded too; the attention skips the queries beyond them."""
-        R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
+        if isinstance(n_valid, PrefixTail):  # (two key segments per task, Conditioned.sample_functions: the tensors travel with the counts)
+            R_t = self.attender.attend_pt(Xt_pt.t, None, None, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
+            live = n_valid.live(B)
+        else:
+            R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
+            live = n_valid > 0
         if not isinstance(self.attender, DotAttender):
-            R_t = R_t * (n_valid > 0).to(R_t.dtype).view(B, 1, 1, 1, 1)
+            R_t = R_t * live.to(R_t.dtype).view(B, 1, 1, 1, 1)
         return R_t
 
     def _attend_into(self, ch, Xc_pt, R, Xt_pt, C, T, tap_x1: bool = False):
