@@ -265,7 +265,9 @@ int npf_mixture_summary(const float *suff, const int32_t *n_valid, int32_t n_z, 
  *           out = c_{m-1} + sum_{k>=m} inv_weights[k] (c_k - c_{k-1}); inv_weights[n_z] = P(K >= k) of the
  *           number-of-samples distribution (host), m = the smallest number of samples it draws.
  * Running logsumexp per task: no [n_z][n_tasks] temporaries (and, with the loss-only Gaussian head above,
- * nothing of size [n_z][n_tasks][targets][dy]). */
+ * nothing of size [n_z][n_tasks][targets][dy]).
+ * A sample with log_w = -inf (modes 1 and 2) is a term of weight 0 wherever it stands, the first sample included, and its
+ * gradient is exactly 0, as with torch.logsumexp.  A task whose samples are ALL -inf is not covered: its result is unspecified. */
 int npf_mc_objective_fwd(const float *log_w, int32_t n_z, int32_t n_tasks, int32_t mode, const float *inv_weights,
                          int32_t m, float *out, void *stream);
 /* d_log_w[n_z][n_tasks] from d_out[n_tasks]; workspace: n_z * n_tasks floats (mode 2 only, else may be NULL). */
@@ -314,7 +316,10 @@ int npf_mha_bwd(const float *q, const float *k, const float *v, const float *out
  * TransformerAttender.forward's layer_norm1(context + queries) (npf/architectures/attention.py:566-575; nn.LayerNorm: biased
  * variance, eps inside the root, gamma / beta [F]).  stats [n_tasks * tiles * 32][2] = (mean, 1 / std) per point, or NULL at inference.
  * npf_add_layernorm_bwd: dx (the gradient of a and of b alike; zero at the padding points) and partials [n_tasks * tiles][2][F] = the
- * tile's sums of dy * xhat and of dy, which the caller adds up over the tiles to dgamma and dbeta. */
+ * tile's sums of dy * xhat and of dy, which the caller adds up over the tiles to dgamma and dbeta.
+ * Padding points (p >= pts_per_task inside the last tile of a task): every point is normalised on its own, and in the backward pass
+ * nothing read at a padding point -- a, b, stats, dy -- reaches dx, the partials or another point: whatever they hold there, NaN
+ * included, has no influence.  (y and stats AT the padding points are whatever the arithmetic makes of a and b there.) */
 int npf_add_layernorm_fwd(const float *a, const float *b, const float *gamma, const float *beta, float eps, int32_t n_tasks,
                           int32_t pts_per_task, int32_t F, float *y, float *stats, void *stream);
 int npf_add_layernorm_bwd(const float *a, const float *b, const float *gamma, const float *stats, const float *dy, int32_t n_tasks,

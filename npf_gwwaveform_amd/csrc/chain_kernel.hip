@@ -1515,10 +1515,12 @@ __global__ __launch_bounds__(64 * WAVES, (MAXB <= 16 && WAVES == 4) ? 2 : 1) voi
         // nn.LayerNorm over the F valid features of the point (biased variance, eps inside the root).
         // Forward: cur = x.  Backward: cur = dy, x reloaded from the saved forward input.
         // gamma / beta are padded with zeros to a multiple of 32 floats (host side) and the padding
-        // features of x / dy are zero, so no per-feature masks are needed: the padding's share of
-        // the variance sum, (Fp - F) mean^2, is subtracted after the reduction.
+        // features of x / dy are zero, so the sums for the mean need no mask.  After centring the
+        // padding features hold -mean: they are set back to zero before the squares are summed
+        // (two-pass variance over the F valid features; subtracting their share (Fp - F) mean^2
+        // after the reduction instead cancels two large numbers on a row with a mean offset).
         const int F = o.i0, FB = ((F + 31) >> 5) * 2;
-        const float invF = 1.f / (float)F, eps = o.f0, npad = (float)(16 * FB - F);
+        const float invF = 1.f / (float)F, eps = o.f0;
         const bool bwd = opc == NPF_OP_LAYERNORM_BWD;
         const float* gam = (const float*)(bwd ? o.p1 : o.p0) + 4 * w.g;
         const float* bet = (const float*)o.p1 + 4 * w.g;  // forward only
@@ -1539,15 +1541,26 @@ __global__ __launch_bounds__(64 * WAVES, (MAXB <= 16 && WAVES == 4) ? 2 : 1) voi
           }
         }
         const float mean = xg_sum(s1) * invF;
+        // The mean is rounded to fp32: half an ulp of 1000 is 3e-5 next to a spread of 1.  x - mean itself is (nearly) exact, so
+        // the mean of the centred values is that rounding error (and the summation's): it is subtracted as well.
+        float s1c = 0.f;
+#pragma unroll
+        for (int b = 0; b < kMaxB16; ++b)
+          if (b < FB) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[b][e] = (16 * b + e < lim) ? x[b][e] - mean : 0.f;
+            s1c += (x[b][0] + x[b][1]) + (x[b][2] + x[b][3]);
+          }
+        const float corr = xg_sum(s1c) * invF;
         float s2 = 0.f;
 #pragma unroll
         for (int b = 0; b < kMaxB16; ++b)
           if (b < FB) {
-            x[b] = x[b] - mean;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[b][e] = (16 * b + e < lim) ? x[b][e] - corr : 0.f;
             s2 += (x[b][0] * x[b][0] + x[b][1] * x[b][1]) + (x[b][2] * x[b][2] + x[b][3] * x[b][3]);
           }
-        const float var = fmaxf((xg_sum(s2) - npad * mean * mean) * invF, 0.f);
-        const float rstd = 1.f / sqrtf(var + eps);
+        const float rstd = 1.f / sqrtf(fmaxf(xg_sum(s2) * invF, 0.f) + eps);
         if (!bwd) {
 #pragma unroll
           for (int b = 0; b < kMaxB16; ++b)
@@ -1574,7 +1587,7 @@ __global__ __launch_bounds__(64 * WAVES, (MAXB <= 16 && WAVES == 4) ? 2 : 1) voi
             if (b < FB) {
 #pragma unroll
               for (int e = 0; e < 4; ++e)
-                cur[b][e] = (16 * b + e < lim) ? rstd * (cur[b][e] - m1 - x[b][e] * m2) : 0.f;
+                cur[b][e] = (pt_ok && 16 * b + e < lim) ? rstd * (cur[b][e] - m1 - x[b][e] * m2) : 0.f;  // (padding points: no gradient)
             }
         }
       }

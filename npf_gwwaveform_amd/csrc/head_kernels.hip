@@ -142,6 +142,9 @@ __global__ __launch_bounds__(256) void gauss_head_bwd_kernel(const float* __rest
 //   mode 2: SUMO: c_k = logsumexp_{j <= k} lw_j - log(k + 1) (0-based k), estimate = c_{m-1} +
 //           sum_{k >= m} inv_w[k] (c_k - c_{k-1})        (npf/losses.py:207-276; inv_w[k] = P(K >= k + 1 - ...) from the host)
 // One thread per task (n_z is tens to hundreds, B thousands): sequential running logsumexp, no [n_z, B] temporaries.
+// A sample with lw = -inf is a term of weight 0 wherever it stands (tested ahead of ``v > mx``: as the first sample it would
+// otherwise give expf(-inf - -inf) = NaN) and gets a gradient of exactly 0, as with torch.logsumexp.  A task whose samples are
+// ALL -inf is left as it is (modes 1 / 2: -inf + log(0)); nothing covers it.
 __global__ void mc_objective_fwd_kernel(const float* __restrict__ lw, int n_z, int B, int mode, const float* __restrict__ inv_w,
                                         int m, float* __restrict__ out) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -155,7 +158,9 @@ __global__ void mc_objective_fwd_kernel(const float* __restrict__ lw, int n_z, i
   float mx = -INFINITY, acc = 0.f, est = 0.f, c_prev = 0.f;  // running logsumexp = mx + log(acc)
   for (int k = 0; k < n_z; ++k) {
     const float v = lw[(size_t)k * B + b];
-    if (v > mx) {
+    if (v == -INFINITY) {
+      // a term of weight 0 (ahead of the comparison: with mx still -inf, v - mx would be NaN)
+    } else if (v > mx) {
       acc = acc * expf(mx - v) + 1.f;
       mx = v;
     } else {
@@ -187,7 +192,9 @@ __global__ void mc_objective_bwd_kernel(const float* __restrict__ lw, int n_z, i
   float mx = -INFINITY, acc = 0.f;
   for (int k = 0; k < n_z; ++k) {
     const float v = lw[(size_t)k * B + b];
-    if (v > mx) {
+    if (v == -INFINITY) {
+      // weight 0, as in the forward kernel
+    } else if (v > mx) {
       acc = acc * expf(mx - v) + 1.f;
       mx = v;
     } else {
@@ -197,7 +204,10 @@ __global__ void mc_objective_bwd_kernel(const float* __restrict__ lw, int n_z, i
   }
   if (mode == 1) {
     const float lse = mx + logf(acc);
-    for (int k = 0; k < n_z; ++k) d_lw[(size_t)k * B + b] = g * expf(lw[(size_t)k * B + b] - lse);
+    for (int k = 0; k < n_z; ++k) {
+      const float v = lw[(size_t)k * B + b];
+      d_lw[(size_t)k * B + b] = v == -INFINITY ? 0.f : g * expf(v - lse);
+    }
     return;
   }
   // SUMO: tail[k] = sum_{K >= k} coef[K] exp(-lse_K), accumulated relative to a running reference to stay in range
@@ -214,7 +224,8 @@ __global__ void mc_objective_bwd_kernel(const float* __restrict__ lw, int n_z, i
       tail = tail * expf(lse - ref) + coef;
       ref = lse;
     }
-    d_lw[(size_t)k * B + b] = g * tail * expf(lw[(size_t)k * B + b] - ref);
+    const float v = lw[(size_t)k * B + b];
+    d_lw[(size_t)k * B + b] = v == -INFINITY ? 0.f : g * tail * expf(v - ref);  // (leading -inf samples: ref is -inf too)
   }
 }
 

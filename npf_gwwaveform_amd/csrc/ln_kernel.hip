@@ -42,12 +42,28 @@ __global__ __launch_bounds__(kLnThreads) void add_layernorm_fwd_kernel(const flo
     }
   }
   const float mean = ln_sum8(s, red, tid) / (float)F;
+  // The stored mean is rounded to fp32 (half an ulp of 1000 is 3e-5 next to a spread of 1); x - mean itself is (nearly) exact, so
+  // the mean of the centred values is that rounding error: it is subtracted as well (the backward pass does the same).
+  float sc = 0.f;
+#pragma unroll
+  for (int n = 0; n < 8; ++n)
+    if (c0 + 8 * n < ncol) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x[n][e] -= mean;
+        sc += x[n][e];
+      }
+    }
+  const float corr = ln_sum8(sc, red, tid) / (float)F;
   float v = 0.f;
 #pragma unroll
   for (int n = 0; n < 8; ++n)
     if (c0 + 8 * n < ncol) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v += (x[n][e] - mean) * (x[n][e] - mean);
+      for (int e = 0; e < 4; ++e) {
+        x[n][e] -= corr;
+        v += x[n][e] * x[n][e];
+      }
     }
   const float rstd = 1.0f / sqrtf(ln_sum8(v, red, tid) / (float)F + eps);
 #pragma unroll
@@ -57,7 +73,7 @@ __global__ __launch_bounds__(kLnThreads) void add_layernorm_fwd_kernel(const flo
       const f32x4 g = *(const f32x4*)(gamma + 4 * c), bt = *(const f32x4*)(beta + 4 * c);
       f32x4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (x[n][e] - mean) * rstd * g[e] + bt[e];
+      for (int e = 0; e < 4; ++e) o[e] = x[n][e] * rstd * g[e] + bt[e];
       *(f32x4*)(y + tile + ((size_t)c * 32 + p) * 4) = o;
     }
   }
@@ -79,20 +95,30 @@ __global__ __launch_bounds__(kLnThreads) void add_layernorm_bwd_kernel(const flo
   const bool live = (int)(blockIdx.x % tiles_per_task) * 32 + p < pts;  // (padding points: no gradient, nothing into dgamma / dbeta)
   const float mean = stats[((size_t)blockIdx.x * 32 + p) * 2], rstd = stats[((size_t)blockIdx.x * 32 + p) * 2 + 1];
   f32x4 xh[8], g[8];
-  float s1 = 0.f, s2 = 0.f;
+  float s1 = 0.f, s2 = 0.f, sc = 0.f;
+  // x - mean - corr as in the forward kernel: corr = the mean of the centred values (the rounding of the stored mean)
 #pragma unroll
   for (int n = 0; n < 8; ++n) {
     const int c = c0 + 8 * n;
     xh[n] = g[n] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (c >= ncol) continue;
     const size_t at = tile + ((size_t)c * 32 + p) * 4;
-    const f32x4 x = *(const f32x4*)(a + at) + *(const f32x4*)(b + at);
+    xh[n] = *(const f32x4*)(a + at) + *(const f32x4*)(b + at) - mean;
+    sc += xh[n][0] + xh[n][1] + xh[n][2] + xh[n][3];
+  }
+  const float corr = ln_sum8(sc, red, tid) / (float)F;
+#pragma unroll
+  for (int n = 0; n < 8; ++n) {
+    const int c = c0 + 8 * n;
+    if (c >= ncol) continue;
+    const size_t at = tile + ((size_t)c * 32 + p) * 4;
+    const f32x4 x = xh[n] - corr;  // (centred)
     f32x4 d = *(const f32x4*)(dy + at);
     if (!live) d = f32x4{0.f, 0.f, 0.f, 0.f};
     const f32x4 gm = *(const f32x4*)(gamma + 4 * c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      xh[n][e] = (x[e] - mean) * rstd;
+      xh[n][e] = live ? x[e] * rstd : 0.f;  // (a, b, stats at a padding point may hold anything, NaN included)
       g[n][e] = d[e];                       // dy (for dgamma / dbeta)
       const float dxh = d[e] * gm[e];
       s1 += dxh;
