@@ -3,7 +3,7 @@
 random context / target split on the device, AttnCNP with transformer attention (what the
 reference's notebooks and shipped checkpoints use), Adam, checkpoint in skorch's layout.
 
-    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged] [--predict] [--rollout]
+    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged] [--predict] [--rollout] [--loo]
 
 Only the import line differs from a script written against the reference:
     from npf import AttnCNP, CNPFLoss                      # reference
@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--rollout", action="store_true",
                     help="after training (fp32): condition on 16 points of one new function with room to grow and draw ONE "
                          "autoregressive sample on a 32-point grid (Conditioned.rollout: query, draw, feed the draw back)")
+    ap.add_argument("--loo", action="store_true",
+                    help="after training (fp32): the leave-one-out check of a 16-point context of one new function, one of whose "
+                         "observations is a glitch -- every point predicted from the other 15 out of one encode (model.loo)")
     ap.add_argument("--out", default="/tmp/npf_example_ckpt")
     args = ap.parse_args()
     dev = "cuda:0"
@@ -108,6 +111,19 @@ def main():
         print("autoregressive sample   x      y0       y1")
         for t in range(0, 32, 4):
             print(f"                     {float(grid[0, t, 0]):7.3f}  {float(sample[0, t, 0]):7.3f}  {float(sample[0, t, 1]):7.3f}")
+    if args.loo and args.dtype == "fp32":  # (the masked route: fp32 only)
+        model.eval()
+        X, Y = functions(1, args.points, dev, seed=10 ** 7)
+        ctx = torch.linspace(0, args.points - 1, 16, device=dev).long()
+        Xc, Yc = X[:, ctx].contiguous(), Y[:, ctx].clone()
+        Yc[0, 7, 1] += 1.0  # (the glitch)
+        p = model.loo(Xc, Yc)  # HeadDistribution [1, 1, 16] x [2]: point i given the other 15
+        log_density = p.log_prob(Yc.unsqueeze(0))[0, 0]
+        resid = ((Yc - p.base_dist.loc[0]) / p.base_dist.scale[0])[0]
+        print("leave-one-out   x     log p(y_i | others)   residual / sigma (y0, y1)")
+        for i in range(16):
+            print(f"             {float(Xc[0, i, 0]):7.3f}  {float(log_density[i]):12.3f}          {float(resid[i, 0]):7.2f} {float(resid[i, 1]):7.2f}"
+                  + ("   <- glitch" if i == 7 else ""))
 
 
 if __name__ == "__main__":

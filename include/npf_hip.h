@@ -29,6 +29,7 @@
  *   npf_gather_points    CntxtTrgtGetter.select              npf/utils/datasplit.py:246-255
  *   npf_masked_attn_fwd/bwd (and _fwd_nq / _bwd_nq: padded queries too), npf_masked_mean_fwd/bwd  DotAttender.forward / torch.mean(R_cntxt, dim=1) of a padded batch
  *                        whose per-task context sizes are device data (no reference counterpart: the reference cuts the batch)
+ *   npf_masked_attn_fwd_loo, npf_loo_mean  the same for every context point over the OTHER points of its task (leave-one-out; inference)
  *   npf_append_points    new context rows behind the rows each task of such a padded batch holds (no reference counterpart)
  *   npf_split_heads/npf_merge_heads  MultiheadAttender._make_multiheaded / _concatenate_multiheads
  *                                                         npf/architectures/attention.py:505-527
@@ -543,6 +544,17 @@ int npf_masked_attn_fwd_prefix(const float *q, const float *k_pre, const float *
                                const float *v_tail, const int32_t *n_tail, const int32_t *n_q_valid, int32_t n_tasks,
                                int32_t n_prefix_tasks, int32_t c_pad, int32_t m_tail, int32_t n_queries, int32_t d, float scale,
                                float *out, void *stream);
+/* Leave-one-out (inference only, no backward, no lse): npf_masked_attn_fwd_nq in which query row t of a task never meets key row t
+ * of that task (row numbers inside the task; q and k / v stay separate tensors):
+ *   out(b, t, :) = sum_{k < n_valid[b], k != t} softmax_{k < n_valid[b], k != t}(scale <Q(b,t,:), K(b,k,:)>) V(b,k,:)
+ * for t < n_q_valid[b], exact zeros for a query without any such key (n_valid[b] <= 1 with t = 0, n_valid[b] == 0) and beyond the
+ * query count.  With q = k = the encoded context points and v = their representations this is, for every context point, the
+ * attention of that point over the OTHER points of its task.  v(b, t, :) has no influence on out(b, t, :), whatever it holds (Inf /
+ * NaN included: the own row's product is not formed).  n_q_valid: DEVICE int32 [n_tasks] as in npf_masked_attn_fwd_nq, or NULL (all
+ * n_queries rows are real).  Same key blocks, fp32 MFMA roles and online softmax as npf_masked_attn_fwd; the results are
+ * deterministic.  Every element of out (whole tiles) is written.  Status: as npf_masked_attn_fwd. */
+int npf_masked_attn_fwd_loo(const float *q, const float *k, const float *v, const int32_t *n_valid, const int32_t *n_q_valid,
+                            int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d, float scale, float *out, void *stream);
 /* out[task][F] (row-major) = mean over the first n_valid[task] points of PT32 tensor R (F % 32 == 0), zeros if n_valid[task] == 0
  * (torch.mean(R_cntxt, dim=1) on the batch cut per task, np.py:95, attnnp.py:181); tiles beyond the count are not read. */
 int npf_masked_mean_fwd(const float *R_pt, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *out,
@@ -550,6 +562,12 @@ int npf_masked_mean_fwd(const float *R_pt, const int32_t *n_valid, int32_t n_tas
 /* dR_pt[task][p][f] (+)= d_out[task][f] / n_valid[task] for p < n_valid[task], 0 beyond (accumulate as npf_mean_agg_bwd). */
 int npf_masked_mean_bwd(const float *d_out, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *dR_pt,
                         int32_t accumulate, void *stream);
+/* Leave-one-out means (inference only): out (PT32 [n_tasks][pts_per_task][F], every element written) row i < n_valid[task] =
+ * (sum over the task's first n_valid[task] rows of R_pt - row i) / (n_valid[task] - 1); zeros for i >= n_valid[task] and where
+ * n_valid[task] <= 1.  The per-task sum is taken inside the launch in the summation order of npf_masked_mean_fwd; tiles beyond the
+ * count are not read. */
+int npf_loo_mean(const float *R_pt, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *out,
+                 void *stream);
 
 /* ---- growing contexts: rows appended at per-task offsets that are device data (csrc/append_kernels.hip) ----------------------
  * For every pair i < n_pairs (<= NPF_APPEND_MAX_PAIRS), task b and j < clamp(n_new[b], 0, n_rows) (n_new == NULL: j < n_rows):

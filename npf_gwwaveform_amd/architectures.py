@@ -414,6 +414,15 @@ class PrefixTail:
         return ((self.n_pre.clamp(0, self.c_pad).repeat(n_tasks // B) + self.n_tail.clamp(0, self.m_tail)) > 0)
 
 
+class LeaveOneOut:
+    """The key counts ``n_valid`` of a padded batch with the request that query row ``t`` of a task shall not see key row ``t`` of that
+    task (``functional.masked_attention_loo``): the queries are the context points themselves, each attends over the others.
+    Handed to ``attend_pt`` in the place of ``n_valid``, inference only."""
+
+    def __init__(self, n_valid):
+        self.n_valid = n_valid
+
+
 def _sample_major(x, S, H, B):
     """Tasks [H, S, B] (``npf_split_heads`` of S x B tasks: task ``h * S B + s * B + b``) -> [S, H, B] (task ``s * B H + h * B + b``, so
     that the kernel's ``j % (B H)`` is ``h * B + b``, the index ``npf_split_heads`` gives head ``h`` of task ``b`` of the prefix), one
@@ -460,7 +469,8 @@ class DotAttender(nn.Module):
         """PT32 in, PT32 out, any number of keys (fused chain up to 256 keys, blocked softmax of
         attention_long.py beyond).  ``n_valid``: device integer tensor [n_tasks], the number of real keys of every task among
         the ``n_keys`` rows (a padded batch): the masked attention kernel (``functional.masked_attention``).  ``n_q_valid`` (with
-        ``n_valid`` only): the number of real queries of every task; the rows beyond come back as zeros and are skipped."""
+        ``n_valid`` only): the number of real queries of every task; the rows beyond come back as zeros and are skipped.
+        ``n_valid`` as a :class:`LeaveOneOut`: the same with query row ``t`` kept from key row ``t`` (inference only)."""
         from .attention_long import long_scaledot_attention
 
         if n_q_valid is not None and n_valid is None:
@@ -470,6 +480,11 @@ class DotAttender(nn.Module):
             w, scale = n_valid, 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
             return FN.masked_attention_prefix(queries_pt, w.k_pre, w.v_pre, w.n_pre, w.k_tail, w.v_tail, w.n_tail, queries_pt.shape[0],
                                               w.n_prefix_tasks, w.c_pad, w.m_tail, n_queries, self.kq_size, scale, n_q_valid=n_q_valid)
+        if isinstance(n_valid, LeaveOneOut):  # (query row t without key row t: NeuralProcessFamily.loo)
+            _no_bf16_masked()
+            scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
+            return FN.masked_attention_loo(queries_pt, keys_pt, values_pt, n_valid.n_valid, queries_pt.shape[0], n_keys, n_queries,
+                                           self.kq_size, scale, n_q_valid=n_q_valid)
         if n_valid is not None:
             _no_bf16_masked()
             scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
@@ -579,7 +594,11 @@ class MultiheadAttender(nn.Module):
             Qp = queries_proj if queries_proj is not None else self._project(queries_pt, B, T, self.query_transform)
             Qh = FN.split_heads(Qp, B, T, d, H)
             Vh = FN.split_heads(self._project(values_pt, B, C, self.value_transform), B, C, self.value_size, H)
-            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=FN.counts_i32(n_valid, B).repeat(H),
+            if isinstance(n_valid, LeaveOneOut):  # (the same route on the leave-one-out launch: the row numbers are those of the task)
+                counts = LeaveOneOut(FN.counts_i32(n_valid.n_valid, B).repeat(H))
+            else:
+                counts = FN.counts_i32(n_valid, B).repeat(H)
+            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=counts,
                                     n_q_valid=None if n_q_valid is None else FN.counts_i32(n_q_valid, B, "n_q_valid").repeat(H))
             return FN.merge_heads(Oh, B, T, self.value_size, H)
         if FN.mha_usable(self.kq_head_size, self.value_head_size, C):

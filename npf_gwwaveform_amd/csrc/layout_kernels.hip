@@ -210,6 +210,35 @@ __global__ void mean_fwd_kernel(const float* __restrict__ R, const int32_t* __re
   if (p == 0 && in_F) *(f32x4*)(out + task * F + 4 * f4) = (!MASKED || n > 0) ? s * (1.f / (float)n) : f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// Leave-one-out means (npf_loo_mean): out[task][i] = (sum over the task's n valid rows - row i) / (n - 1) for i < n, zeros for
+// i >= n and where n <= 1.  The geometry of mean_fwd_kernel<true> and its summation order for the per-task sum (every lane holds it
+// after the butterfly); the second walk reads the valid tiles again and writes every tile -- those beyond the count are not read.
+__global__ void loo_mean_kernel(const float* __restrict__ R, const int32_t* __restrict__ n_valid, int pts, int F,
+                                float* __restrict__ out) {
+  const int tiles = (pts + 31) / 32;
+  const int p = threadIdx.x & 31, f4 = blockIdx.x * 8 + (threadIdx.x >> 5);
+  const size_t task = blockIdx.y;
+  const int n = clamp_count(n_valid, task, pts);
+  const size_t at = task * tiles * (size_t)(F * 32) + pt_off(f4, p);
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t * 32 < n; ++t)
+    if (t * 32 + p < n) s += *(const f32x4*)(R + at + (size_t)t * F * 32);
+#pragma unroll
+  for (int off = 16; off >= 1; off >>= 1)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] += __shfl_xor(s[j], off);
+  const float others = (float)(n - 1);
+  for (int t = 0; t < tiles; ++t) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (n > 1 && t * 32 + p < n) {
+      const f32x4 r = *(const f32x4*)(R + at + (size_t)t * F * 32);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = (s[j] - r[j]) / others;
+    }
+    *(f32x4*)(out + at + (size_t)t * F * 32) = v;
+  }
+}
+
 template <bool MASKED>
 __global__ void mean_bwd_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ n_valid, int n_tasks, int pts, int F,
                                 float* __restrict__ dR, int accumulate) {
@@ -380,6 +409,17 @@ extern "C" int npf_masked_mean_bwd(const float* d_out, const int32_t* n_valid, i
   const size_t total = (size_t)n_tasks * ((pts + 31) / 32) * (F / 4) * 32;
   hipLaunchKernelGGL(npf::mean_bwd_kernel<true>, dim3(npf::grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, d_out, n_valid,
                      n_tasks, pts, F, dR_pt, accumulate);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_loo_mean(const float* R_pt, const int32_t* n_valid, int32_t n_tasks, int32_t pts, int32_t F, float* out,
+                            void* stream) {
+  if (!R_pt || !n_valid || !out || n_tasks < 0 || pts <= 0 || F <= 0 || (F & 31)) return NPF_EINVAL;
+  if ((((uintptr_t)R_pt) | ((uintptr_t)out)) & 15) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  if (n_tasks > 65535) return NPF_EINVAL;  // (the task is the grid's y index)
+  hipLaunchKernelGGL(npf::loo_mean_kernel, dim3(F / 32, n_tasks), dim3(256), 0, (hipStream_t)stream, R_pt, n_valid, pts, F, out);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }

@@ -27,6 +27,9 @@
 // of one conditioned context read the context's keys / values from one copy and keep only the rows they drew themselves.  Each
 // segment ends as the single one does (blocks beyond the count skipped, the last block's rows beyond it zeros / -inf); the running
 // maximum, sum and accumulator carry over the switch.  With every tail count 0 the block sequence is that of npf_masked_attn_fwd.
+//
+// Leave-one-out (npf_masked_attn_fwd_loo, a forward kernel of its own, inference only): query row t of a task attends over the
+// task's keys without key row t -- the predictive of every context point from the others, out of one encode of the context.
 #include "npf_common.hpp"
 
 namespace npf {
@@ -206,6 +209,119 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_prefix_kernel(const float
                                                                     int n_keys, int T, int Fp, int d, float scale,
                                                                     const MkTail<true> tl) {
   masked_attn_fwd_body<DP, NQ, true>(Q, K, V, n_valid, n_q_valid, O, nullptr, n_keys, T, Fp, d, scale, tl);
+}
+
+// Leave-one-out (npf_masked_attn_fwd_loo, inference only): the forward kernel's geometry, staging, operand roles and online softmax
+// with one exclusion -- query row t never meets key row t of its task (row numbers inside the task; Q and K / V stay separate tensors).
+// A kernel of its own rather than a flag of the shared body, so that the instances above keep their schedules.  What the exclusion
+// adds to the walk:
+//  * a query can be without an admissible key in a block (or in the whole walk) although the block was staged: the running maximum
+//    may stay -inf, so the exponentials are taken against 0 then (exp(-inf - 0) = 0, never exp(-inf + inf)); a block that holds
+//    nothing for a query leaves its m, l and accumulator as they were, and a query without any key ends at l = 0 -> exact zeros;
+//  * p = 0 is not enough to keep v[t] out of row t (0 * Inf = NaN on the matrix unit).  The 16 queries of a wave are rows
+//    own0 .. own0 + 15, and the key sub-blocks are 16 rows at multiples of 16, so the own rows of a wave are exactly one sub-block:
+//    its P V product runs on the vector unit, key by key, with the value row replaced by zeros in the lanes of the query it belongs
+//    to.  Every other sub-block is the MFMA product of the forward kernel.
+// n_q_valid may be null: every one of the T queries is real.
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_fwd_loo_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                 const float* __restrict__ V, const int32_t* __restrict__ n_valid,
+                                                                 const int32_t* __restrict__ n_q_valid, float* __restrict__ O,
+                                                                 int n_keys, int T, int Fp, int d, float scale) {
+  using G = MkGeom<DP>;
+  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
+  __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
+  __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int qblocks = (T + 63) >> 6;
+  const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int nv = clamp_count(n_valid, b, n_keys);  // (uniform over the workgroup)
+  const int nq = n_q_valid != nullptr ? clamp_count(n_q_valid, b, T) : T;
+  const int own0 = qb * 64 + wave * 16;  // the wave's queries, and the key sub-block that holds their own rows
+  const int q = own0 + c;
+  if (qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zeros, no key staged
+    if (q < tilesT * 32) {
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+        if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    return;
+  }
+  const bool live = q < nq;
+  float Qq[NKC];  // the lane's query as an operand: Q[q][4 kc + g]
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc) Qq[kc] = (live && 4 * kc < d) ? Q[mk_pt(b, tilesT, Fp, q, 4 * kc) + g] : 0.f;
+  f32x4 o[NDT];  // O^T[dv = 16 dt + 4 g + i][q = c], not yet divided by l
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  for (int key0 = 0; key0 < nv; key0 += KB) {
+    __syncthreads();
+    mk_stage<DP, KB, LDK>(K, b, tilesC, Fp, d, key0, nv, Ks, tid);
+    mk_stage<DP, KB, LDV>(V, b, tilesC, Fp, d, key0, nv, Vs, tid);
+    __syncthreads();
+    f32x4 S[NSB];  // S^T[key = key0 + 16 sb + 4 g + i][q = c]
+    float bm = -INFINITY;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) acc = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], acc);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = key0 + 16 * sb + 4 * g + i;
+        acc[i] = (key < nv && key != q) ? acc[i] * scale : -INFINITY;  // (beyond the count, and the query's own row)
+        bm = fmaxf(bm, acc[i]);
+      }
+      S[sb] = acc;
+    }
+    // (the block's only real key may be the query's own: its maximum, and the running one, can be -inf here)
+    const float m_new = fmaxf(m, mk_max4(bm));
+    const float m_ref = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = expf(m - m_ref);  // (0 while m = -inf; 1 where the block holds nothing for the query)
+    float ps = 0.f;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        S[sb][i] = expf(S[sb][i] - m_ref);  // (exp(-inf) = 0 beyond the count and on the own row)
+        ps += S[sb][i];
+      }
+    l = l * alpha + mk_sum4(ps);
+    m = m_new;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) {
+      if (key0 + 16 * sb == own0) {  // (uniform over the wave) the sub-block of the own rows: key by key, the own value row as zeros
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+          const float p = __shfl(S[sb][kk & 3], c + 16 * (kk >> 2));  // P[key own0 + kk][q = c]
+          const bool own = kk == c;
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) {
+            const f32x4 v = *(const f32x4*)(Vs + (16 * sb + kk) * LDV + 16 * dt + 4 * g);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[dt][i] = fmaf(own ? 0.f : v[i], p, o[dt][i]);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) o[dt] = mk_mfma(Vs[(16 * sb + 4 * g + j) * LDV + 16 * dt + c], S[sb][j], o[dt]);
+      }
+    }
+  }
+  const bool filled = live && l > 0.f;  // (no admissible key, a query beyond the count, the tile's rows beyond T: zeros)
+  const float inv = filled ? 1.f / l : 0.f;
+  if (q < tilesT * 32) {
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+      if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = filled ? o[dt] * inv : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
 }
 
 // d_q: the forward pass's geometry.  dS^T = scale P^T (dP^T - D), P from the log-sum-exp, D[q] = <dO[q], O[q]>.
@@ -521,6 +637,24 @@ extern "C" int npf_masked_attn_fwd_prefix(const float* q, const float* k_pre, co
 #undef MK_PFX_NQ
 #undef MK_PFX
 #undef MK_PFX_I
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_attn_fwd_loo(const float* q, const float* k, const float* v, const int32_t* n_valid,
+                                       const int32_t* n_q_valid, int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d,
+                                       float scale, float* out, void* stream) {
+  const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
+  if (rc != NPF_OK) return rc;
+  if (!out || mk_misaligned(out)) return NPF_EINVAL;
+  if (n_tasks == 0 || n_queries == 0) return NPF_OK;
+  const int Fp = npf::round_up(d, 32);
+  const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define MK_LOO(DP) \
+  hipLaunchKernelGGL((npf::masked_attn_fwd_loo_kernel<DP>), grid, block, 0, st, q, k, v, n_valid, n_q_valid, out, n_keys, n_queries, Fp, d, scale)
+  MK_DISPATCH(MK_LOO);
+#undef MK_LOO
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }

@@ -562,6 +562,53 @@ def masked_attention_prefix(q_pt: torch.Tensor, k_pre: torch.Tensor, v_pre: torc
     return out
 
 
+def masked_attention_loo(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, n_keys: int,
+                         n_queries: int, d: int, scale: float, n_q_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PT32 [n_tasks, n_queries, d]: :func:`masked_attention` in which query row ``t`` of a task does not see key row ``t`` of that
+    task (``npf_masked_attn_fwd_loo``) -- with the encoded context points as queries and keys, every context point attends over the
+    OTHER points of its task.  Exact zeros where no other key is left (a task with one point or none) and beyond ``n_q_valid``;
+    ``v_pt`` row ``t`` has no influence on row ``t`` of the result.  Counts as in :func:`masked_attention`: device int32 / int64, read
+    by the kernel only.  Inference only -- there is no backward pass, and a call in which an input requires grad is refused."""
+    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
+        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
+    if n_tasks < 0 or n_keys < 0 or n_queries < 0:
+        raise ValueError(f"negative size: n_tasks={n_tasks}, n_keys={n_keys}, n_queries={n_queries}")
+    tensors = (q_pt, k_pt, v_pt)
+    if any(t.requires_grad for t in tensors):
+        raise RuntimeError("masked_attention_loo is inference only (no backward pass): detach the inputs")
+    for what, t, shape in (("q_pt", q_pt, pt_shape(n_tasks, n_queries, d)), ("k_pt", k_pt, pt_shape(n_tasks, n_keys, d)),
+                           ("v_pt", v_pt, pt_shape(n_tasks, n_keys, d))):
+        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
+            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    n_valid = counts_i32(n_valid, n_tasks)
+    if n_q_valid is not None:
+        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
+    q_pt, k_pt, v_pt = (t.detach().contiguous() for t in tensors)
+    out = torch.empty(pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
+    L.check(L.load().npf_masked_attn_fwd_loo(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid),
+                                             _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks, n_keys, n_queries, d,
+                                             float(scale), L.ptr(out), L.stream_ptr()), "npf_masked_attn_fwd_loo")
+    return out
+
+
+def loo_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
+    """PT32 [n_tasks, pts, F]: row ``i < n_valid[task]`` is the mean over the task's first ``n_valid[task]`` points WITHOUT point ``i``,
+    ``(sum - R[i]) / (n - 1)`` (``npf_loo_mean``: the sum is taken in the launch, in the order of :func:`masked_mean`); zeros beyond the
+    count and where a task has one point or none.  Counts as in :func:`masked_attention`.  Inference only: a call in which the input
+    requires grad is refused."""
+    if n_tasks < 0 or pts < 1 or F < 1:
+        raise ValueError(f"loo_mean needs n_tasks >= 0, pts >= 1 and F >= 1, got {n_tasks}, {pts}, {F}")
+    if R_pt.requires_grad:
+        raise RuntimeError("loo_mean is inference only (no backward pass): detach the input")
+    if tuple(R_pt.shape) != tuple(pt_shape(n_tasks, pts, F)) or R_pt.dtype != torch.float32:
+        raise ValueError(f"R_pt must be an fp32 PT32 tensor of shape {tuple(pt_shape(n_tasks, pts, F))}, got {R_pt.dtype} {tuple(R_pt.shape)}")
+    n_valid = counts_i32(n_valid, n_tasks)
+    R_pt = R_pt.detach().contiguous()
+    out = torch.empty_like(R_pt)  # (written whole)
+    L.check(L.load().npf_loo_mean(L.ptr(R_pt), _iptr(n_valid), n_tasks, pts, pad32(F), L.ptr(out), L.stream_ptr()), "npf_loo_mean")
+    return out
+
+
 def masked_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
     """Mean over the first ``n_valid[task]`` points of a PT32 tensor -> row-major [n_tasks, pad32(F)] (zeros where a task has none):
     ``torch.mean(R, dim=1)`` (npf/neuralproc/np.py:95, attnnp.py:181) of the batch cut per task; counts as in :func:`masked_attention`."""

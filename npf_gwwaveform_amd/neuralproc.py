@@ -26,8 +26,8 @@ import torch.nn as nn
 from torch.distributions import Independent, Normal
 
 from . import functional as FN
-from .architectures import (MLP, DotAttender, MergeFlatInputs, MultiheadAttender, PrefixTail, SelfAttention, get_attender,
-                            merge_flat_input)
+from .architectures import (MLP, DotAttender, LeaveOneOut, MergeFlatInputs, MultiheadAttender, PrefixTail, SelfAttention,
+                            get_attender, merge_flat_input)
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
@@ -214,6 +214,36 @@ class Conditioned:
             Y[:, s:s + chunk] = y
             self.extend(x, y)
         return Y
+
+    def loo(self) -> HeadDistribution:
+        """The leave-one-out predictive of the stored context: for every context point ``i`` of every task, p(y_i | the task's other
+        points) at ``x_i`` -> :class:`HeadDistribution` with batch shape [1, B, rows] (rows: ``capacity``, or C), whose target counts
+        are the live context counts (rows beyond: ``loc = 0``, ``scale = 1``) -- see :meth:`NeuralProcessFamily.loo`.  Computed from
+        the stored rows in one masked attention launch with the diagonal excluded (CNP: one ``npf_loo_mean`` launch) and the decoder;
+        nothing is encoded again and the state is only read -- after ``extend`` the new points are included.  Accepted on states that
+        hold the row tensors: every ``condition_with_capacity`` state, and ``condition`` states of attentive models that were not
+        stored for the fused target side.  Inference only, no host sync."""
+        m = self._model
+        m._refuse_loo()
+        if self.capacity is not None:
+            Xc_pt, R_pts, rows, n = self._Xc_pt, self._R_pts, self.capacity, self.n_cntxt
+        else:
+            padded_kind = self.n_cntxt is not None and self.C > 0
+            if not m._attentive:
+                raise ValueError("loo: this context holds the pooled representation only; condition with a capacity "
+                                 "(condition_with_capacity)")
+            if self._fused_t and not padded_kind:
+                raise ValueError("loo: this context was stored for the fused target side (images of keys / values only); "
+                                 "condition with counts (n_cntxt=...) or a capacity (condition_with_capacity)")
+            if self.C == 0:
+                raise ValueError("loo: no context points")
+            Xc_pt, R_pts, rows, n = self._Xc_pt, self._R, self.C, self.n_cntxt
+        if Xc_pt is None or R_pts is None:
+            raise ValueError("loo: this state does not hold the encoded context points and their representations")
+        with torch.no_grad():
+            if n is None:  # (conditioned without counts: every task holds all C rows)
+                n = torch.full((self.B,), rows, dtype=torch.int32, device=Xc_pt.t.device)
+            return m._loo_from(Xc_pt, R_pts, n, self.B, rows)
 
     def _function_sampler(self, X_trgt, n_samples, eps, chunk):
         """The argument checks of :meth:`sample_functions` -> (its per-call state, ``eps``, ``chunk``)."""
@@ -573,8 +603,8 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         together with its own device counts (a copy of ``n_cntxt``, or C for every task), and :meth:`Conditioned.extend` /
         :meth:`Conditioned.rollout` add observations to it in place.  Such a model always runs the padded route of ``forward``
         (``n_cntxt``) with ``capacity`` key rows: masked attention / mean stop at the counts and never read the rows beyond.  Stored:
-        the encoded context points (attentive models) and the per-point representations (every model: CNP / LNP re-pool their mean
-        from them).  A latent model draws ``eps = randn([n_z, B, 1, z_dim])`` once -- the draw ``rsample`` makes in ``condition`` -- keeps
+        the encoded context points and the per-point representations (every model: CNP / LNP re-pool their mean from the latter
+        and decode ``Conditioned.loo`` at the former).  A latent model draws ``eps = randn([n_z, B, 1, z_dim])`` once -- the draw ``rsample`` makes in ``condition`` -- keeps
         it (``Conditioned.eps``) and sets ``z_samples = loc + scale * eps``, again after every ``extend``.  Not implemented, as with
         ``n_cntxt``: ``is_self_attn=True`` and the bf16 compute mode."""
         self._refuse_unimplemented("capacity")
@@ -594,14 +624,14 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
             dev = X_cntxt.device
             # (zeros: the rows beyond the counts are never read, but they stay finite for whoever looks at the state)
             R_pts = PTensor(torch.zeros(pt_shape(B, capacity, self.r_dim), device=dev), capacity, self.r_dim)
-            Xc_pt = PTensor(torch.zeros(pt_shape(B, capacity, self.x_transf_dim), device=dev), capacity, self.x_transf_dim) \
-                if self._attentive else None
+            # (the encoded points of every model: the keys of an attentive one, and the decoder's x of ``Conditioned.loo``)
+            Xc_pt = PTensor(torch.zeros(pt_shape(B, capacity, self.x_transf_dim), device=dev), capacity, self.x_transf_dim)
             counts = torch.zeros(B, dtype=torch.int32, device=dev)
             post = Conditioned(self, Xc_pt, R_pts if self._attentive else torch.zeros(B, 1, self.r_dim, device=dev), None, None, counts,
                                B, C, False, capacity=capacity, R_pts=R_pts)
             if C > 0:
                 Xn_pt, Rn_pts = self._encode_points(X_cntxt, Y_cntxt)
-                pairs = [(Rn_pts.t, R_pts.t, self.r_dim)] + ([(Xn_pt.t, Xc_pt.t, self.x_transf_dim)] if self._attentive else [])
+                pairs = [(Rn_pts.t, R_pts.t, self.r_dim), (Xn_pt.t, Xc_pt.t, self.x_transf_dim)]
                 FN.append_points(pairs, counts, n_cntxt, B, C, capacity)
             post._refresh()
             if n_z is not None:
@@ -609,6 +639,55 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
                 post.eps = torch.randn(n_z, B, 1, self.z_dim, device=dev)
                 post.z_samples = q.base_dist.loc + q.base_dist.scale * post.eps
         return post
+
+    def loo(self, X_cntxt, Y_cntxt, n_cntxt=None) -> HeadDistribution:
+        """The leave-one-out predictive of a context: for every task ``b`` and context point ``i``, p(y_i | the task's other points)
+        at ``x_i`` -- what ``forward`` returns for the context cut to the other ``n - 1`` points with ``x_i`` as the only target -- out
+        of ONE encode of the context.  Without a self-attention encoder the representation of a context point depends on that point
+        alone, so this is exact: the attentive models run one masked attention launch whose queries are the encoded context points
+        and in which query ``i`` does not see key ``i`` (``npf_masked_attn_fwd_loo``), CNP takes ``(sum - r_i) / (n - 1)``
+        (``npf_loo_mean``); then the decoder and the masked head of the padded route.  -> :class:`HeadDistribution` with batch shape
+        [1, B, C] and event shape [y_dim] whose target counts are the context counts: ``log_prob(Y_cntxt)`` is the per-point LOO log
+        density, ``summary(probs)`` / ``base_dist`` work as on any other; rows at and beyond ``n_cntxt[b]`` (optional per-task sizes of
+        a padded context, default C for every task) have ``loc = 0`` / ``scale = 1``, and a task with a single point is predicted from
+        the empty context.  Inference only (``torch.no_grad`` semantics, the model's mode respected), no host sync and no range
+        check: one captured graph serves every mix of counts.  Not implemented: ``is_self_attn=True``, the bf16 compute mode and the
+        latent models (q(z | C without i) differs per left-out point, and the decoder takes one z per task)."""
+        self._refuse_loo()
+        if X_cntxt.dim() != 3 or Y_cntxt.dim() != 3 or X_cntxt.shape[:2] != Y_cntxt.shape[:2]:
+            raise ValueError(f"X_cntxt / Y_cntxt must be [B, C, x_dim] / [B, C, y_dim], got {list(X_cntxt.shape)} / {list(Y_cntxt.shape)}")
+        B, C, _ = X_cntxt.shape
+        if C == 0:
+            raise ValueError("loo: no context points")
+        with torch.no_grad():
+            if n_cntxt is not None:
+                n_cntxt = self._check_counts(n_cntxt, X_cntxt, "n_cntxt")
+            self._check_tensors(X_cntxt, Y_cntxt)
+            if n_cntxt is None:
+                n_cntxt = torch.full((B,), C, dtype=torch.int32, device=X_cntxt.device)
+            Xc_pt, R_pts = self._encode_points(X_cntxt, Y_cntxt)
+            return self._loo_from(Xc_pt, R_pts, n_cntxt, B, C)
+
+    def _refuse_loo(self):
+        if self.encoded_path != "deterministic":
+            raise NotImplementedError("loo is not implemented for latent models (LNP / AttnLNP): q(z | C without i) differs per "
+                                      "left-out point and the decoder takes one z per task")
+        self._refuse_unimplemented("loo")
+
+    def _loo_from(self, Xc_pt, R_pts, n, B, rows) -> HeadDistribution:
+        """The leave-one-out predictive from the encoded context points and their per-point representations (PTensors of ``rows`` rows
+        per task, ``n`` [B] device int32 of them real)."""
+        return self._head(self._loo_suffstat(Xc_pt, R_pts, n, B, rows), None, B, rows, n_trgt=n)
+
+    def _decode_pointwise(self, R_t, X1_pt, B, T):
+        """The decoder on one representation per target (PT32 ``R_t`` [B, T, r]) as the padded route of the attentive models runs it."""
+        from . import x6
+
+        if x6.decoder_side_usable(self, T):
+            return x6.decoder_side(self, R_t, X1_pt, T)
+        ch = Chain(B, T, X1_pt.device, wg_per_task=True)
+        ch.input_pt(R_t, self.r_dim)
+        return self.decoder.finish_rows(ch, x1_pt=X1_pt)
 
     def _encode_points(self, X, Y):
         """The per-point stages of the context side on [B, N, .] points -> (encoded points, per-point representations), PTensors of
@@ -913,6 +992,11 @@ class CNP(NeuralProcessFamily):
     def _target_suffstat(self, Xc_pt, z_samples, R, Xt_pt, B, C, T, n_valid=None, n_q_valid=None):
         return self._decode_taskvec(Xt_pt, R.reshape(B, self.r_dim), B, T, B)
 
+    def _loo_suffstat(self, Xc_pt, R_pts, n, B, rows):
+        """Point ``i`` is decoded at ``x_i`` from the mean over the task's other points (zeros where there is none, as
+        ``encode_globally`` at C = 0)."""
+        return self._decode_pointwise(FN.loo_mean(R_pts.t, n, B, rows, self.r_dim), Xc_pt.t, B, rows)
+
 
 class LNP(LatentNeuralProcessFamily, CNP):
     """(Latent) neural process (npf/neuralproc/np.py:113-163)."""
@@ -1018,12 +1102,19 @@ class AttnCNP(NeuralProcessFamily):
         if isinstance(n_valid, PrefixTail):  # (two key segments per task, Conditioned.sample_functions: the tensors travel with the counts)
             R_t = self.attender.attend_pt(Xt_pt.t, None, None, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
             live = n_valid.live(B)
+        elif isinstance(n_valid, LeaveOneOut):  # (the targets are the context points: a task needs two of them to have a key left)
+            R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
+            live = n_valid.n_valid > 1
         else:
             R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
             live = n_valid > 0
         if not isinstance(self.attender, DotAttender):
             R_t = R_t * live.to(R_t.dtype).view(B, 1, 1, 1, 1)
         return R_t
+
+    def _loo_suffstat(self, Xc_pt, R_pts, n, B, rows):
+        """The padded route with the encoded context points as targets and the diagonal of the attention excluded."""
+        return self._target_suffstat(Xc_pt, None, R_pts, Xc_pt, B, rows, rows, n_valid=LeaveOneOut(n), n_q_valid=n)
 
     def _attend_into(self, ch, Xc_pt, R, Xt_pt, C, T, tap_x1: bool = False):
         """cur of ``ch`` <- attention of the targets over the context (attnnp.py:118-131): fused into
