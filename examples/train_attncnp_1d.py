@@ -3,7 +3,7 @@
 random context / target split on the device, AttnCNP with transformer attention (what the
 reference's notebooks and shipped checkpoints use), Adam, checkpoint in skorch's layout.
 
-    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged] [--predict] [--rollout] [--loo]
+    python examples/train_attncnp_1d.py [--steps 200] [--dtype bf16] [--per-task-contexts | --ragged] [--predict] [--rollout] [--loo] [--score]
 
 Only the import line differs from a script written against the reference:
     from npf import AttnCNP, CNPFLoss                      # reference
@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--loo", action="store_true",
                     help="after training (fp32): the leave-one-out check of a 16-point context of one new function, one of whose "
                          "observations is a glitch -- every point predicted from the other 15 out of one encode (model.loo)")
+    ap.add_argument("--score", action="store_true",
+                    help="after training: score held-out targets of 64 new functions under the predictive distribution "
+                         "(HeadDistribution.score): mean log density, mean CRPS and the PIT decile counts")
     ap.add_argument("--out", default="/tmp/npf_example_ckpt")
     args = ap.parse_args()
     dev = "cuda:0"
@@ -124,6 +127,19 @@ def main():
         for i in range(16):
             print(f"             {float(Xc[0, i, 0]):7.3f}  {float(log_density[i]):12.3f}          {float(resid[i, 0]):7.2f} {float(resid[i, 1]):7.2f}"
                   + ("   <- glitch" if i == 7 else ""))
+    if args.score:
+        if args.dtype == "fp32":
+            model.eval()
+        X, Y = functions(64, args.points, dev, seed=10 ** 7 + 1)
+        ctx = torch.linspace(0, args.points - 1, 16, device=dev).long()
+        held = torch.ones(args.points, dtype=torch.bool, device=dev)
+        held[ctx] = False
+        Xt, Yt = X[:, held].contiguous(), Y[:, held].contiguous()
+        with torch.no_grad():
+            s = model(X[:, ctx].contiguous(), Y[:, ctx].contiguous(), Xt)[0].score(Yt)  # Score(log_density, pit, crps), [64, T, 2] each
+        print(f"held-out targets: mean log density {float(s.log_density.mean()):.3f}, mean CRPS {float(s.crps.mean()):.4f} (per output dim)")
+        # (no padded rows here; with n_trgt the histogram must be masked by the counts: rows beyond them hold pit = 0.5)
+        print("PIT decile counts (flat for a calibrated model):", torch.histc(s.pit, bins=10, min=0.0, max=1.0).long().tolist())
 
 
 if __name__ == "__main__":

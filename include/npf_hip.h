@@ -19,6 +19,7 @@
  *   npf_gauss_head_bwd   autograd of the above
  *   npf_masked_gauss_head_fwd/bwd  the same over a batch of padded targets whose per-task sizes are device data
  *   npf_mixture_summary  mean / std / quantiles of the predictive mixture over the latent samples (inference; no reference counterpart)
+ *   npf_mixture_score    log density / PIT / CRPS of an observation under that mixture (inference; no reference counterpart)
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -256,6 +257,21 @@ int npf_masked_gauss_head_bwd(const float *suff, const float *loc, const float *
 int npf_mixture_summary(const float *suff, const int32_t *n_valid, int32_t n_z, int32_t n_tasks, int32_t pts, int32_t dy,
                         int32_t homoskedastic, const float *z_p, int32_t n_probs, const float *probs, float *mean, float *std,
                         float *quant, void *stream);
+
+/* Scores of observations under the same mixture (the counterpart of npf_mixture_summary evaluated at y; no reference counterpart).
+ * suff as above, Y[n_tasks][pts][dy].  With mu_k, sg_k the components of element (b, t, d), u_k = (y - mu_k) / sg_k and K = n_z, one
+ * launch writes the outputs whose pointer is not NULL ([n_tasks][pts][dy] each; at least one must be given, a NULL one costs nothing):
+ *   log_density = logsumexp_k(-u_k^2 / 2 - log sg_k - log sqrt(2 pi)) - log K   (maximum subtracted; a component at -inf has weight 0)
+ *   pit         = 1/K sum_k Phi(u_k)                                             (Phi through erfc, on the side that does not cancel)
+ *   crps        = 1/K sum_k A(y - mu_k, sg_k) - 1/(2 K^2) sum_{i,j} A(mu_i - mu_j, sqrt(sg_i^2 + sg_j^2)),
+ *                 A(m, s) = 2 s phi(m / s) + m erf(m / (s sqrt 2));  the pair sum is evaluated as K (K - 1) / 2 off-diagonal terms
+ *                 plus the diagonal 2 sg_i / sqrt(pi), its terms in fp32, their sum in double.
+ * The scores are marginal per output dimension.  1 <= n_z <= 128, dy <= 16, n_tasks <= 65535, pts * dy <= 2^30.  n_valid: NULL or a
+ * DEVICE int32 [n_tasks] tensor (clamped to [0, pts]): task b owns its first n_valid[b] points, the homoskedastic pooling covers
+ * those, suff and Y beyond are never read and the rows beyond get log_density = 0, crps = 0 (a sum over the points needs no mask)
+ * and pit = 0.5 (a PIT histogram must be masked by the counts).  A non-finite Y[b][t][d] reaches the outputs of that element only. */
+int npf_mixture_score(const float *suff, const float *Y, const int32_t *n_valid, int32_t n_z, int32_t n_tasks, int32_t pts,
+                      int32_t dy, int32_t homoskedastic, float *log_density, float *pit, float *crps, void *stream);
 
 /* ---- Monte-Carlo objectives over the latent samples (npf/losses.py:126-276) ------------ */
 /* log_w: row-major [n_z][n_tasks], the log weight of latent sample k for task b: sum_t log p(y_t | z_k), plus

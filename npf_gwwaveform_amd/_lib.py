@@ -139,6 +139,7 @@ SIGNATURES = {
     "npf_masked_gauss_head_fwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p]),
     "npf_masked_gauss_head_bwd": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "npf_mixture_summary": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
+    "npf_mixture_score": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "npf_masked_mean_fwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "npf_masked_mean_bwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _i32, _p]),
     "npf_append_points": (C.c_int, [C.POINTER(NpfAppendPair), _i32, _p, _p, _i32, _i32, _i32, _p]),

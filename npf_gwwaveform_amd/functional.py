@@ -233,6 +233,51 @@ def mixture_summary(suff: torch.Tensor, n_z: int, dy: int, homoskedastic: bool, 
     return mean, std, quant
 
 
+SCORE_NAMES = ("log_density", "pit", "crps")
+
+
+def check_want(want) -> tuple:
+    """``want`` as a tuple of names out of ``SCORE_NAMES``, at least one; anything else is a ValueError."""
+    if isinstance(want, str) or not isinstance(want, (tuple, list)):
+        raise ValueError(f"want must be a tuple / list of names out of {SCORE_NAMES}, got {want!r}")
+    for w in want:
+        if w not in SCORE_NAMES:
+            raise ValueError(f"want: unknown score {w!r} (known: {SCORE_NAMES})")
+    if not want:
+        raise ValueError(f"want must name at least one of {SCORE_NAMES}")
+    return tuple(want)
+
+
+def mixture_score(suff: torch.Tensor, Y: torch.Tensor, n_z: int, dy: int, homoskedastic: bool, n_valid: Optional[torch.Tensor] = None,
+                  want=SCORE_NAMES):
+    """(log_density, pit, crps) at the observations ``Y`` [B, pts, dy] of the equal-weight mixture over the latent samples of the
+    Gaussians the head makes of the raw decoder output ``suff`` [n_z * B, pts, 2 * dy] (row ``k * B + b``): [B, pts, dy] each,
+    marginal per output dimension; the entries ``want`` does not name are ``None`` and cost nothing.  One ``npf_mixture_score``
+    launch, inference only (no autograd), no host sync; nothing of size [n_z, B, pts, dy] is written.  ``log_density`` is the log of
+    the mixture density, ``pit`` its CDF at ``Y`` (the probability integral transform) and ``crps`` the continuous ranked probability
+    score in closed form (``include/npf_hip.h`` has the formulae).  ``n_valid``: device integer tensor [B], the real points of every
+    task of a padded batch; rows beyond hold ``log_density = 0``, ``crps = 0`` (a sum over the points needs no mask) and
+    ``pit = 0.5``: a PIT histogram must be masked by the counts."""
+    want = check_want(want)
+    if not suff.is_cuda or suff.dtype != torch.float32 or not Y.is_cuda or Y.dtype != torch.float32:
+        raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    n_rows, pts, two_dy = suff.shape
+    if two_dy != 2 * dy or n_z < 1 or n_rows % n_z != 0:
+        raise ValueError(f"suff of shape {tuple(suff.shape)} does not hold n_z={n_z} samples of a {dy}-dimensional head")
+    if n_z > MIXTURE_MAX_NZ:
+        raise NotImplementedError(f"mixture_score covers up to {MIXTURE_MAX_NZ} latent samples (got {n_z})")
+    B = n_rows // n_z
+    if tuple(Y.shape) != (B, pts, dy):
+        raise ValueError(f"Y must have shape [B={B}, pts={pts}, dy={dy}], got {tuple(Y.shape)}")
+    suff, Y = suff.detach().contiguous(), Y.detach().contiguous()
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    out = [torch.empty((B, pts, dy), dtype=torch.float32, device=suff.device) if name in want else None for name in SCORE_NAMES]
+    L.check(L.load().npf_mixture_score(L.ptr(suff), L.ptr(Y), _iptr(nv) if nv is not None else None, n_z, B, pts, dy,
+                                       int(homoskedastic), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.stream_ptr()),
+            "npf_mixture_score")
+    return tuple(out)
+
+
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------
 MC_MEAN, MC_LOGMEANEXP, MC_SUMO = 0, 1, 2
 

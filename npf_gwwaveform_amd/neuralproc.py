@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, LeaveOneOut, MergeFlatInputs, Mult
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction"]
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score"]
 
 
 def MultivariateNormalDiag(loc, scale_diag):
@@ -48,6 +48,14 @@ class Prediction(NamedTuple):
     std: torch.Tensor        # [B, T, y_dim]
     quantiles: torch.Tensor  # [len(probs), B, T, y_dim]
     probs: Tuple[float, ...]
+
+
+class Score(NamedTuple):
+    """Scores of observed values under the predictive distribution (:meth:`HeadDistribution.score`), per target point and output
+    dimension; the entries that were not asked for are ``None``."""
+    log_density: Optional[torch.Tensor]  # [B, T, y_dim] log of the predictive density at y
+    pit: Optional[torch.Tensor]          # [B, T, y_dim] predictive CDF at y (probability integral transform)
+    crps: Optional[torch.Tensor]         # [B, T, y_dim] continuous ranked probability score
 
 
 class HeadDistribution(Independent):
@@ -96,6 +104,23 @@ class HeadDistribution(Independent):
         n_z = self.batch_shape[0]
         mean, std, quant = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, probs=probs, n_valid=self._n_trgt)
         return Prediction(mean, std, quant, probs)
+
+
+    def score(self, Y_trgt, want=FN.SCORE_NAMES) -> Score:
+        """How well the predictive distribution fits the observed ``Y_trgt`` [B, T, y_dim] -> :class:`Score` of [B, T, y_dim]
+        tensors: ``log_density`` (log of the predictive density at y), ``pit`` (the predictive CDF at y: uniform on (0, 1) for a
+        calibrated model) and ``crps`` (the continuous ranked probability score, in the units of y, smaller is better).  The
+        predictive distribution is the one :meth:`summary` describes: marginal over the latent samples (the equal-weight mixture
+        of the ``n_z`` Gaussians) and marginal per output dimension -- for CNP / AttnCNP, whose predictive is a product of
+        independent Gaussians, the joint log density of a point is the sum of ``log_density`` over the last axis.  One
+        ``npf_mixture_score`` launch on the raw decoder output: ``loc`` / ``scale`` are not materialised (``base_dist`` is left
+        alone), nothing of size [n_z, B, T, y_dim] is written, no host sync; inference only.  ``want``: the names to compute, the
+        others come back ``None`` and cost nothing.  With padded targets (``n_trgt``; for :meth:`NeuralProcessFamily.loo` the
+        context counts) the rows beyond a task's count hold ``log_density = 0`` and ``crps = 0``, so a sum over T needs no mask,
+        and ``pit = 0.5``: a PIT histogram must be masked by the counts."""
+        want = FN.check_want(want)
+        n_z = self.batch_shape[0]
+        return Score(*FN.mixture_score(self._suff, Y_trgt, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt, want=want))
 
 
 class Conditioned:
