@@ -211,8 +211,13 @@ __global__ void mean_fwd_kernel(const float* __restrict__ R, const int32_t* __re
 }
 
 // Leave-one-out means (npf_loo_mean): out[task][i] = (sum over the task's n valid rows - row i) / (n - 1) for i < n, zeros for
-// i >= n and where n <= 1.  The geometry of mean_fwd_kernel<true> and its summation order for the per-task sum (every lane holds it
-// after the butterfly); the second walk reads the valid tiles again and writes every tile -- those beyond the count are not read.
+// i >= n and where n <= 1.  The geometry of mean_fwd_kernel<true>; the per-task sum (every lane holds it after the butterfly) is
+// held in DOUBLE, per-lane partial sums and butterfly alike, and so are the subtraction and the division: row i's result is what
+// is left of the sum once row i is taken out, and where that row is the task's largest an fp32 sum has already rounded the others
+// away (one row x 1e5 among 40: 1e-3 of that row's result; in double a sum of 2^9 fp32 terms within a factor 2^20 of each other is
+// exact).  One rounding, to fp32, at the store: with n = 2 row 0 is row 1 bit for bit.  The second walk reads the valid tiles again
+// and writes every tile -- those beyond the count are not read.  The double additions are one per tile, lane and feature; the
+// kernel is bound by its two reads.
 __global__ void loo_mean_kernel(const float* __restrict__ R, const int32_t* __restrict__ n_valid, int pts, int F,
                                 float* __restrict__ out) {
   const int tiles = (pts + 31) / 32;
@@ -220,20 +225,24 @@ __global__ void loo_mean_kernel(const float* __restrict__ R, const int32_t* __re
   const size_t task = blockIdx.y;
   const int n = clamp_count(n_valid, task, pts);
   const size_t at = task * tiles * (size_t)(F * 32) + pt_off(f4, p);
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
   for (int t = 0; t * 32 < n; ++t)
-    if (t * 32 + p < n) s += *(const f32x4*)(R + at + (size_t)t * F * 32);
+    if (t * 32 + p < n) {
+      const f32x4 r = *(const f32x4*)(R + at + (size_t)t * F * 32);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] += (double)r[j];
+    }
 #pragma unroll
   for (int off = 16; off >= 1; off >>= 1)
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] += __shfl_xor(s[j], off);
-  const float others = (float)(n - 1);
+  const double others = (double)(n - 1);
   for (int t = 0; t < tiles; ++t) {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (n > 1 && t * 32 + p < n) {
       const f32x4 r = *(const f32x4*)(R + at + (size_t)t * F * 32);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = (s[j] - r[j]) / others;
+      for (int j = 0; j < 4; ++j) v[j] = (float)((s[j] - (double)r[j]) / others);
     }
     *(f32x4*)(out + at + (size_t)t * F * 32) = v;
   }

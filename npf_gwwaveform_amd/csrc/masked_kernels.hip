@@ -222,6 +222,8 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_prefix_kernel(const float
 //    own0 .. own0 + 15, and the key sub-blocks are 16 rows at multiples of 16, so the own rows of a wave are exactly one sub-block:
 //    its P V product runs on the vector unit, key by key, with the value row replaced by zeros in the lanes of the query it belongs
 //    to.  Every other sub-block is the MFMA product of the forward kernel.
+//  * the score contraction is added in segments of 64 features (below): at the 128- and 256-wide instances the scores, and so the
+//    rows that have no own key (q >= the key count), are NOT bit for bit those of the forward kernel; up to 64 features they are.
 // n_q_valid may be null: every one of the T queries is real.
 template <int DP>
 __global__ __launch_bounds__(256) void masked_attn_fwd_loo_kernel(const float* __restrict__ Q, const float* __restrict__ K,
@@ -230,6 +232,7 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_loo_kernel(const float* _
                                                                  int n_keys, int T, int Fp, int d, float scale) {
   using G = MkGeom<DP>;
   constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
+  constexpr int SEG = NKC < 16 ? NKC : 16;  // MFMA steps (of 4 features) per segment of the score contraction
   __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
   __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -266,9 +269,17 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_loo_kernel(const float* _
     float bm = -INFINITY;
 #pragma unroll
     for (int sb = 0; sb < NSB; ++sb) {
+      // the contraction in segments of 64 features, each a chain of its own from 0, the segments added afterwards: an fp32 chain
+      // rounds at the size of its running sum, and scores that share a large component (|q . k| of 1600 at 256 features) are told
+      // apart only by what those roundings leave.  One segment up to 64 features: the bits of the plain chain.
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kc = 0; kc < NKC; ++kc) acc = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], acc);
+      for (int k0 = 0; k0 < NKC; k0 += SEG) {
+        f32x4 part = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kc = k0; kc < k0 + SEG; ++kc) part = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], part);
+        acc = k0 == 0 ? part : acc + part;
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int key = key0 + 16 * sb + 4 * g + i;

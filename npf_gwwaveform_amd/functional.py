@@ -638,8 +638,9 @@ def masked_attention_loo(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Ten
 
 def loo_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
     """PT32 [n_tasks, pts, F]: row ``i < n_valid[task]`` is the mean over the task's first ``n_valid[task]`` points WITHOUT point ``i``,
-    ``(sum - R[i]) / (n - 1)`` (``npf_loo_mean``: the sum is taken in the launch, in the order of :func:`masked_mean`); zeros beyond the
-    count and where a task has one point or none.  Counts as in :func:`masked_attention`.  Inference only: a call in which the input
+    ``(sum - R[i]) / (n - 1)`` (``npf_loo_mean``: the sum is taken in the launch and held in double, as are the subtraction and the
+    division, with one rounding to fp32 -- a row that dwarfs the others of its task still gets their mean, and with two points the rows
+    swap bit for bit; the bits are not those of :func:`masked_mean`); zeros beyond the count and where a task has one point or none.  Counts as in :func:`masked_attention`.  Inference only: a call in which the input
     requires grad is refused."""
     if n_tasks < 0 or pts < 1 or F < 1:
         raise ValueError(f"loo_mean needs n_tasks >= 0, pts >= 1 and F >= 1, got {n_tasks}, {pts}, {F}")
