@@ -31,6 +31,8 @@
  *   npf_masked_attn_fwd/bwd (and _fwd_nq / _bwd_nq: padded queries too), npf_masked_mean_fwd/bwd  DotAttender.forward / torch.mean(R_cntxt, dim=1) of a padded batch
  *                        whose per-task context sizes are device data (no reference counterpart: the reference cuts the batch)
  *   npf_masked_attn_fwd_loo, npf_loo_mean  the same for every context point over the OTHER points of its task (leave-one-out; inference)
+ *   npf_masked_attn_fwd_weighted, npf_weighted_mean  the same for S replicates of one stored context that differ in a weight per key
+ *                        (bootstrap multiplicities, fold masks; inference)
  *   npf_append_points    new context rows behind the rows each task of such a padded batch holds (no reference counterpart)
  *   npf_split_heads/npf_merge_heads  MultiheadAttender._make_multiheaded / _concatenate_multiheads
  *                                                         npf/architectures/attention.py:505-527
@@ -584,6 +586,30 @@ int npf_masked_mean_bwd(const float *d_out, const int32_t *n_valid, int32_t n_ta
  * count are not read. */
 int npf_loo_mean(const float *R_pt, const int32_t *n_valid, int32_t n_tasks, int32_t pts_per_task, int32_t F, float *out,
                  void *stream);
+/* Reweighted contexts (inference only, no backward, no lse): n_tasks = S * n_ctx_tasks replicates of ONE stored copy of the context.
+ * Task j reads the queries (q: PT32 [n_ctx_tasks][n_queries][d], shared by the replicates), keys, values and counts (n_valid /
+ * n_q_valid: DEVICE int32 [n_ctx_tasks], n_q_valid may be NULL) of context task j % n_ctx_tasks -- the rule of
+ * npf_masked_attn_fwd_prefix -- and row j of w (row-major [n_tasks][n_keys], fp32, on the device): a weight per key.  Key k of task j
+ * is admissible iff k < n_valid[j % n_ctx_tasks] and 0 < w[j][k] < +inf (a weight that is 0, negative, NaN or Inf removes the key):
+ *   out(j, q, :) = sum_adm w_k exp(scale <Q, K_k>) V_k / sum_adm w_k exp(scale <Q, K_k>),    out: PT32 [n_tasks][n_queries][d],
+ * exact zeros for a query without an admissible key and beyond n_q_valid.  An integer weight is "the point appears w times": the
+ * result is that of npf_masked_attn_fwd on the context with its rows repeated.  The K / V rows of an inadmissible key never meet a
+ * multiply, whatever they hold.  The running maximum is over scale <Q, K_k> + log w_k of the admissible keys of the replicate alone.
+ * With every weight 1.0 and S = 1 the result is BIT-IDENTICAL to npf_masked_attn_fwd_nq (npf_masked_attn_fwd with n_q_valid NULL) on
+ * the same tensors: the same key blocks, summation order and online softmax.  The host never reads w or the counts: the launch sits in
+ * a captured graph and sees new weights at every replay.  Deterministic; every element of out (whole tiles) is written.  With heads
+ * as extra tasks the caller orders them replicate-major (task s * (B H) + h * B + b) over keys / values split by npf_split_heads.
+ * Status: NPF_EINVAL (nothing launched) for d % 4 != 0, d > 256, n_ctx_tasks <= 0, n_tasks % n_ctx_tasks != 0, a negative size or
+ * misaligned pointers. */
+int npf_masked_attn_fwd_weighted(const float *q, const float *k, const float *v, const float *w, const int32_t *n_valid,
+                                 const int32_t *n_q_valid, int32_t n_tasks, int32_t n_ctx_tasks, int32_t n_keys, int32_t n_queries,
+                                 int32_t d, float scale, float *out, void *stream);
+/* out[j][F] (row-major, as npf_masked_mean_fwd; F % 32 == 0) = sum_adm w[j][k] R(j % n_ctx_tasks, k, :) / sum_adm w[j][k] over the
+ * admissible points (as above) of context task j % n_ctx_tasks of PT32 tensor R_pt [n_ctx_tasks][pts_per_task][F]; zeros where the
+ * admissible weights sum to 0.  w: row-major [n_tasks][pts_per_task].  Tiles beyond the count and rows without weight are not read.
+ * Sums and the division are held in double in a fixed order: one rounding, and a second launch gives the same bits. */
+int npf_weighted_mean(const float *R_pt, const float *w, const int32_t *n_valid, int32_t n_tasks, int32_t n_ctx_tasks,
+                      int32_t pts_per_task, int32_t F, float *out, void *stream);
 
 /* ---- growing contexts: rows appended at per-task offsets that are device data (csrc/append_kernels.hip) ----------------------
  * For every pair i < n_pairs (<= NPF_APPEND_MAX_PAIRS), task b and j < clamp(n_new[b], 0, n_rows) (n_new == NULL: j < n_rows):

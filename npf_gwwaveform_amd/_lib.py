@@ -136,6 +136,8 @@ SIGNATURES = {
     "npf_masked_attn_fwd_prefix": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _p, _p]),
     "npf_masked_attn_fwd_loo": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_float, _p, _p]),
     "npf_loo_mean": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p]),
+    "npf_masked_attn_fwd_weighted": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_float, _p, _p]),
+    "npf_weighted_mean": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "npf_masked_gauss_head_fwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p]),
     "npf_masked_gauss_head_bwd": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "npf_mixture_summary": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),

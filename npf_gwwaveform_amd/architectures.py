@@ -423,6 +423,26 @@ class LeaveOneOut:
         self.n_valid = n_valid
 
 
+class KeyWeights:
+    """The key counts ``n_valid`` [B] of a padded batch with a non-negative weight per (replicate, task, key), ``w`` float [S, B, C]
+    (``functional.masked_attention_weighted``): the ``S * B`` tasks handed to ``attend_pt`` are S replicates of the B context tasks in
+    replicate-major order (task ``s * B + b``), all attending over the ONE stored copy of the B tasks' keys / values, replicate ``s``
+    with softmax probabilities ``p_k ~ w[s, b, k] exp(s_k)``; a weight that is 0 (or negative, NaN, Inf) removes the key.  Handed to
+    ``attend_pt`` in the place of ``n_valid``, inference only.  The queries (and ``n_q_valid``) arrive for all S * B tasks but are
+    shared by the replicates: the attention reads those of the first replicate.  For an attender with learned projections the
+    caller-facing weights stay [S, B, C]; the attender expands them per head to [S, H, B, C], as it repeats the counts."""
+
+    def __init__(self, w, n_valid, S):
+        self.w, self.n_valid, self.S = w, n_valid, int(S)
+
+    def live(self, n_tasks):
+        """bool [n_tasks]: does the replicate task have an admissible key (computed on the device, no host read)."""
+        w = self.w.reshape(n_tasks, -1)
+        C = w.shape[1]
+        below = torch.arange(C, device=w.device).view(1, C) < self.n_valid.clamp(0, C).repeat(self.S).view(n_tasks, 1)
+        return ((w > 0) & (w < math.inf) & below).any(dim=1)
+
+
 def _sample_major(x, S, H, B):
     """Tasks [H, S, B] (``npf_split_heads`` of S x B tasks: task ``h * S B + s * B + b``) -> [S, H, B] (task ``s * B H + h * B + b``, so
     that the kernel's ``j % (B H)`` is ``h * B + b``, the index ``npf_split_heads`` gives head ``h`` of task ``b`` of the prefix), one
@@ -485,6 +505,12 @@ class DotAttender(nn.Module):
             scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
             return FN.masked_attention_loo(queries_pt, keys_pt, values_pt, n_valid.n_valid, queries_pt.shape[0], n_keys, n_queries,
                                            self.kq_size, scale, n_q_valid=n_q_valid)
+        if isinstance(n_valid, KeyWeights):  # (S replicates of one stored context, a weight per key: Conditioned.reweighted)
+            _no_bf16_masked()
+            kw, scale = n_valid, 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
+            B0 = kw.n_valid.shape[0]  # (the queries and their counts are shared by the replicates: those of the first one are read)
+            return FN.masked_attention_weighted(queries_pt[:B0], keys_pt, values_pt, kw.w, kw.n_valid, kw.S * B0, B0, n_keys, n_queries,
+                                                self.kq_size, scale, n_q_valid=None if n_q_valid is None else n_q_valid[:B0])
         if n_valid is not None:
             _no_bf16_masked()
             scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
@@ -587,6 +613,21 @@ class MultiheadAttender(nn.Module):
             n_tail = FN.counts_i32(w.n_tail, B, "n_tail").view(S, 1, B0).expand(S, H, B0).reshape(S * H * B0)
             heads = PrefixTail(w.k_pre, w.v_pre, FN.counts_i32(w.n_pre, B0, "n_pre").repeat(H), Kt, Vt, n_tail, H * B0, w.c_pad, w.m_tail)
             Oh = self.dot.attend_pt(Qh, None, None, C, T, n_valid=heads)
+            return FN.merge_heads(_head_major(Oh, S, H, B0), B, T, self.value_size, H)
+        if isinstance(n_valid, KeyWeights):
+            # heads as tasks over one stored context: keys / values projected and split ONCE (task h * B0 + b), the shared queries
+            # likewise; the weights are expanded per head to [S, H, B0, C] so that row s * (B0 H) + h * B0 + b is replicate s of
+            # head task h * B0 + b, and the result goes back head-major for the merge
+            _no_bf16_masked()
+            kw = n_valid
+            S, B0 = kw.S, B // kw.S
+            Kh = FN.split_heads(self._project(keys_pt, B0, C, self.key_transform), B0, C, d, H)
+            Vh = FN.split_heads(self._project(values_pt, B0, C, self.value_transform), B0, C, self.value_size, H)
+            Qh = FN.split_heads(self._project(queries_pt[:B0], B0, T, self.query_transform), B0, T, d, H)
+            w = FN.key_weights_f32(kw.w, B, C).view(S, 1, B0, C).expand(S, H, B0, C).contiguous()
+            heads = KeyWeights(w, FN.counts_i32(kw.n_valid, B0).repeat(H), S)
+            nq = None if n_q_valid is None else FN.counts_i32(n_q_valid, B, "n_q_valid")[:B0].repeat(H)
+            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=heads, n_q_valid=nq)
             return FN.merge_heads(_head_major(Oh, S, H, B0), B, T, self.value_size, H)
         if n_valid is not None:
             _no_bf16_masked()

@@ -248,6 +248,47 @@ __global__ void loo_mean_kernel(const float* __restrict__ R, const int32_t* __re
   }
 }
 
+// Weighted means of replicates (npf_weighted_mean): out[j][f] = sum_k w[j][k] R[j % n_ctx_tasks][k][f] / sum_k w[j][k] over the
+// admissible points of context task j % n_ctx_tasks (k below its count, 0 < w < +inf), zeros where there is none -- one stored copy
+// of R serves every replicate.  The geometry of mean_fwd_kernel<true> with the task and the feature block folded into blockIdx.x (the
+// replicates can outnumber a grid's y range).  Products (exact), per-lane sums, butterfly and the division are held in double, as in
+// loo_mean_kernel, with one rounding to fp32 at the store; the order is fixed, so a second launch gives the same bits.  Tiles beyond
+// the count are not read, and neither is the row of a point without weight.
+__global__ void weighted_mean_kernel(const float* __restrict__ R, const float* __restrict__ W, const int32_t* __restrict__ n_valid,
+                                     int n_ctx_tasks, int pts, int F, float* __restrict__ out) {
+  const int tiles = (pts + 31) / 32, fblocks = F / 32;
+  const int p = threadIdx.x & 31, f4 = (blockIdx.x % fblocks) * 8 + (threadIdx.x >> 5);
+  const size_t task = blockIdx.x / fblocks, bc = task % n_ctx_tasks;
+  const int n = clamp_count(n_valid, bc, pts);
+  const float* base = R + bc * tiles * (size_t)(F * 32) + pt_off(f4, p);
+  const float* wrow = W + task * pts;
+  double s[4] = {0.0, 0.0, 0.0, 0.0}, ws = 0.0;
+  for (int t = 0; t * 32 < n; ++t)
+    if (t * 32 + p < n) {
+      const float w = wrow[t * 32 + p];
+      if (w > 0.f && w < INFINITY) {  // (NaN fails both comparisons)
+        const f32x4 r = *(const f32x4*)(base + (size_t)t * F * 32);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] += (double)w * (double)r[j];
+        ws += (double)w;
+      }
+    }
+#pragma unroll
+  for (int off = 16; off >= 1; off >>= 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] += __shfl_xor(s[j], off);
+    ws += __shfl_xor(ws, off);
+  }
+  if (p == 0) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (ws > 0.0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = (float)(s[j] / ws);
+    }
+    *(f32x4*)(out + task * F + 4 * f4) = v;
+  }
+}
+
 template <bool MASKED>
 __global__ void mean_bwd_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ n_valid, int n_tasks, int pts, int F,
                                 float* __restrict__ dR, int accumulate) {
@@ -429,6 +470,19 @@ extern "C" int npf_loo_mean(const float* R_pt, const int32_t* n_valid, int32_t n
   if (n_tasks == 0) return NPF_OK;
   if (n_tasks > 65535) return NPF_EINVAL;  // (the task is the grid's y index)
   hipLaunchKernelGGL(npf::loo_mean_kernel, dim3(F / 32, n_tasks), dim3(256), 0, (hipStream_t)stream, R_pt, n_valid, pts, F, out);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_weighted_mean(const float* R_pt, const float* w, const int32_t* n_valid, int32_t n_tasks, int32_t n_ctx_tasks,
+                                 int32_t pts, int32_t F, float* out, void* stream) {
+  if (!R_pt || !w || !n_valid || !out || n_tasks < 0 || n_ctx_tasks <= 0 || n_tasks % n_ctx_tasks != 0) return NPF_EINVAL;
+  if (pts <= 0 || F <= 0 || (F & 31)) return NPF_EINVAL;
+  if (((((uintptr_t)R_pt) | ((uintptr_t)out)) & 15) || (((uintptr_t)w) & 3)) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  if ((size_t)n_tasks * (F / 32) > 0x7fffffffu) return NPF_EINVAL;  // (task and feature block are the grid's x index)
+  hipLaunchKernelGGL(npf::weighted_mean_kernel, dim3((unsigned)n_tasks * (F / 32)), dim3(256), 0, (hipStream_t)stream, R_pt, w, n_valid,
+                     n_ctx_tasks, pts, F, out);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }

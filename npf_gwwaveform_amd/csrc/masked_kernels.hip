@@ -30,6 +30,11 @@
 //
 // Leave-one-out (npf_masked_attn_fwd_loo, a forward kernel of its own, inference only): query row t of a task attends over the
 // task's keys without key row t -- the predictive of every context point from the others, out of one encode of the context.
+//
+// Per-replicate key weights (npf_masked_attn_fwd_weighted, a forward kernel of its own, inference only): S replicates of every context
+// task attend over ONE stored copy of its keys / values, each with its own non-negative weight per key (p_k ~ w_k exp(s_k): bootstrap
+// multiplicities, fold masks, down-weighted points).  With every weight 1.0 and S = 1 the result is bit-identical to
+// npf_masked_attn_fwd_nq on the same tensors.
 #include "npf_common.hpp"
 
 namespace npf {
@@ -325,6 +330,126 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_loo_kernel(const float* _
           for (int dt = 0; dt < NDT; ++dt) o[dt] = mk_mfma(Vs[(16 * sb + 4 * g + j) * LDV + 16 * dt + c], S[sb][j], o[dt]);
       }
     }
+  }
+  const bool filled = live && l > 0.f;  // (no admissible key, a query beyond the count, the tile's rows beyond T: zeros)
+  const float inv = filled ? 1.f / l : 0.f;
+  if (q < tilesT * 32) {
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+      if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = filled ? o[dt] * inv : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+// Per-replicate key weights (npf_masked_attn_fwd_weighted, a forward kernel of its own, inference only): task j = s * n_ctx_tasks + b
+// is replicate s of context task b = j % n_ctx_tasks.  It reads the queries, keys, values and counts of task b -- ONE stored copy of
+// the context serves every replicate -- and row j of W, a weight per key: p_k ~ w_k exp(s_k).  A key is admissible iff it lies below
+// the count and 0 < w < +inf.  The forward kernel's geometry, staging, operand roles, key blocks and online softmax, with:
+//  * the weight is per key and task, not per query, so an inadmissible key is staged as zeros in its K AND its V row and its score set
+//    to -inf: whatever those rows hold (NaN / Inf included) never meets a multiply -- no vector-unit side path as in the LOO kernel;
+//  * the score is scale <q, k> + log w, and the running maximum is taken over THAT, over the admissible keys of the replicate alone:
+//    a replicate whose highest-scoring key has weight 0 never sees that key's score.  log 1 = 0 and s + 0 = s exactly, so with every
+//    weight 1.0 and one replicate the walk, the summation order and the bits are those of npf_masked_attn_fwd / _nq;
+//  * a staged block can hold no admissible key: the running maximum may stay -inf, the exponentials are taken against 0 then (as in
+//    the LOO kernel), and a query without any admissible key ends at l = 0 -> exact zeros.
+// n_q_valid may be null: every one of the T queries is real.
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_fwd_weighted_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                      const float* __restrict__ V, const float* __restrict__ W,
+                                                                      const int32_t* __restrict__ n_valid,
+                                                                      const int32_t* __restrict__ n_q_valid, float* __restrict__ O,
+                                                                      int n_ctx_tasks, int n_keys, int T, int Fp, int d, float scale) {
+  using G = MkGeom<DP>;
+  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
+  __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
+  __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
+  __shared__ __attribute__((aligned(16))) float Lw[KB];  // log w of the block's keys, -inf where the key is not admissible
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int qblocks = (T + 63) >> 6;
+  const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
+  const int bc = b % n_ctx_tasks;  // the context task whose rows and counts the replicate reads
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int nv = clamp_count(n_valid, bc, n_keys);  // (uniform over the workgroup)
+  const int nq = n_q_valid != nullptr ? clamp_count(n_q_valid, bc, T) : T;
+  const float* __restrict__ wrow = W + (size_t)b * n_keys;
+  const int q = qb * 64 + wave * 16 + c;
+  if (qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zeros, no key staged
+    if (q < tilesT * 32) {
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+        if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    return;
+  }
+  const bool live = q < nq;
+  float Qq[NKC];  // the lane's query as an operand: Q[q][4 kc + g]
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc) Qq[kc] = (live && 4 * kc < d) ? Q[mk_pt(bc, tilesT, Fp, q, 4 * kc) + g] : 0.f;
+  f32x4 o[NDT];  // O^T[dv = 16 dt + 4 g + i][q = c], not yet divided by l
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  for (int key0 = 0; key0 < nv; key0 += KB) {
+    __syncthreads();
+    // mk_stage for K and V at once, with the rows of inadmissible keys as zeros (the weight is read below the count only)
+    for (int i = tid; i < KB * (DP / 4); i += 256) {
+      const int p = i % KB, f4 = i / KB, key = key0 + p;
+      f32x4 x = {0.f, 0.f, 0.f, 0.f}, y = {0.f, 0.f, 0.f, 0.f};
+      if (key < nv && 4 * f4 < d) {
+        const float wk = wrow[key];
+        if (wk > 0.f && wk < INFINITY) {
+          x = *(const f32x4*)(K + mk_pt(bc, tilesC, Fp, key, 4 * f4));
+          y = *(const f32x4*)(V + mk_pt(bc, tilesC, Fp, key, 4 * f4));
+        }
+      }
+      *(float2*)(Ks + p * LDK + 4 * f4) = float2{x[0], x[1]};
+      *(float2*)(Ks + p * LDK + 4 * f4 + 2) = float2{x[2], x[3]};
+      *(float2*)(Vs + p * LDV + 4 * f4) = float2{y[0], y[1]};
+      *(float2*)(Vs + p * LDV + 4 * f4 + 2) = float2{y[2], y[3]};
+    }
+    if (tid < KB) {
+      const int key = key0 + tid;
+      const float wk = key < nv ? wrow[key] : 0.f;
+      Lw[tid] = (wk > 0.f && wk < INFINITY) ? logf(wk) : -INFINITY;  // (NaN fails both comparisons)
+    }
+    __syncthreads();
+    f32x4 S[NSB];  // S^T[key = key0 + 16 sb + 4 g + i][q = c]
+    float bm = -INFINITY;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) acc = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], acc);
+      const f32x4 lw = *(const f32x4*)(Lw + 16 * sb + 4 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        acc[i] = lw[i] > -INFINITY ? acc[i] * scale + lw[i] : -INFINITY;  // (beyond the count, and the keys without weight)
+        bm = fmaxf(bm, acc[i]);
+      }
+      S[sb] = acc;
+    }
+    // (the block may hold no admissible key: its maximum, and the running one, can be -inf here)
+    const float m_new = fmaxf(m, mk_max4(bm));
+    const float m_ref = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = expf(m - m_ref);  // (0 while m = -inf; 1 where the block holds nothing for the replicate)
+    float ps = 0.f;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        S[sb][i] = expf(S[sb][i] - m_ref);  // (exp(-inf) = 0 for an inadmissible key)
+        ps += S[sb][i];
+      }
+    l = l * alpha + mk_sum4(ps);
+    m = m_new;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) o[dt] = mk_mfma(Vs[(16 * sb + 4 * g + j) * LDV + 16 * dt + c], S[sb][j], o[dt]);
   }
   const bool filled = live && l > 0.f;  // (no admissible key, a query beyond the count, the tile's rows beyond T: zeros)
   const float inv = filled ? 1.f / l : 0.f;
@@ -666,6 +791,26 @@ extern "C" int npf_masked_attn_fwd_loo(const float* q, const float* k, const flo
   hipLaunchKernelGGL((npf::masked_attn_fwd_loo_kernel<DP>), grid, block, 0, st, q, k, v, n_valid, n_q_valid, out, n_keys, n_queries, Fp, d, scale)
   MK_DISPATCH(MK_LOO);
 #undef MK_LOO
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_attn_fwd_weighted(const float* q, const float* k, const float* v, const float* w, const int32_t* n_valid,
+                                            const int32_t* n_q_valid, int32_t n_tasks, int32_t n_ctx_tasks, int32_t n_keys,
+                                            int32_t n_queries, int32_t d, float scale, float* out, void* stream) {
+  if (n_ctx_tasks <= 0 || n_tasks < 0 || n_tasks % n_ctx_tasks != 0) return NPF_EINVAL;
+  const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
+  if (rc != NPF_OK) return rc;
+  if (!out || mk_misaligned(out) || (n_keys > 0 && !w) || (((uintptr_t)w) & 3)) return NPF_EINVAL;
+  if (n_tasks == 0 || n_queries == 0) return NPF_OK;
+  const int Fp = npf::round_up(d, 32);
+  const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define MK_WGT(DP)                                                                                                                   \
+  hipLaunchKernelGGL((npf::masked_attn_fwd_weighted_kernel<DP>), grid, block, 0, st, q, k, v, w, n_valid, n_q_valid, out, n_ctx_tasks, \
+                     n_keys, n_queries, Fp, d, scale)
+  MK_DISPATCH(MK_WGT);
+#undef MK_WGT
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }

@@ -655,6 +655,80 @@ def loo_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, 
     return out
 
 
+def key_weights_f32(w: torch.Tensor, n_tasks: int, n_keys: int, what: str = "w") -> torch.Tensor:
+    """The per-(task, key) weights as the contiguous device fp32 [n_tasks, n_keys] tensor the reweighting kernels read: any float
+    tensor with ``n_tasks * n_keys`` elements whose leading dims multiply to ``n_tasks``; a contiguous fp32 tensor is used as given
+    (a view, no copy), so weights overwritten in place are seen by a replayed graph.  The values are never read by the host."""
+    if not isinstance(w, torch.Tensor) or not w.is_floating_point():
+        raise ValueError(f"{what} must be a float device tensor [..., {n_keys}] with {n_tasks} rows, got "
+                         f"{w.dtype if isinstance(w, torch.Tensor) else type(w).__name__}")
+    if w.dim() < 2 or w.shape[-1] != n_keys or w.numel() != n_tasks * n_keys:
+        raise ValueError(f"{what} must hold one weight per (task, key): {n_tasks} rows of {n_keys}, got {list(w.shape)}")
+    if not w.is_cuda:
+        raise ValueError(f"{what} must live on the device (its values are read by the kernels, never by the host)")
+    return w.detach().to(torch.float32).contiguous().view(n_tasks, n_keys)
+
+
+def masked_attention_weighted(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor,
+                              n_tasks: int, n_ctx_tasks: int, n_keys: int, n_queries: int, d: int, scale: float,
+                              n_q_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PT32 [n_tasks, n_queries, d]: ``n_tasks = S * n_ctx_tasks`` replicates of :func:`masked_attention` over ONE stored copy of the
+    context (``npf_masked_attn_fwd_weighted``).  Task ``j`` reads the queries, keys, values and counts of context task
+    ``j % n_ctx_tasks`` (``q_pt`` PT32 [n_ctx_tasks, n_queries, d], ``k_pt`` / ``v_pt`` PT32 [n_ctx_tasks, n_keys, d], ``n_valid`` /
+    ``n_q_valid`` [n_ctx_tasks]) and row ``j`` of ``w`` (float [n_tasks, n_keys], or [S, n_ctx_tasks, n_keys]): softmax probabilities
+    ``p_k ~ w_k exp(s_k)`` over the keys below the count with ``0 < w_k < inf`` -- a weight that is 0, negative, NaN or Inf removes
+    the key, an integer weight is "the point appears w times".  Exact zeros where no key is admissible and beyond ``n_q_valid``; with
+    every weight 1.0 and one replicate the bits of :func:`masked_attention`.  Counts and weights are read by the kernel only.
+    Inference only -- there is no backward pass, and a call in which an input requires grad is refused."""
+    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
+        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
+    if n_ctx_tasks < 1 or n_tasks < 0 or n_tasks % n_ctx_tasks != 0:
+        raise ValueError(f"n_tasks={n_tasks} must be a multiple of n_ctx_tasks={n_ctx_tasks} >= 1 (task j reads context task j % n_ctx_tasks)")
+    if n_keys < 0 or n_queries < 0:
+        raise ValueError(f"negative size: n_keys={n_keys}, n_queries={n_queries}")
+    tensors = (q_pt, k_pt, v_pt)
+    if any(t.requires_grad for t in tensors) or (isinstance(w, torch.Tensor) and w.requires_grad):
+        raise RuntimeError("masked_attention_weighted is inference only (no backward pass): detach the inputs")
+    for what, t, shape in (("q_pt", q_pt, pt_shape(n_ctx_tasks, n_queries, d)), ("k_pt", k_pt, pt_shape(n_ctx_tasks, n_keys, d)),
+                           ("v_pt", v_pt, pt_shape(n_ctx_tasks, n_keys, d))):
+        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
+            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    w = key_weights_f32(w, n_tasks, n_keys)
+    n_valid = counts_i32(n_valid, n_ctx_tasks)
+    if n_q_valid is not None:
+        n_q_valid = counts_i32(n_q_valid, n_ctx_tasks, "n_q_valid")
+    q_pt, k_pt, v_pt = (t.detach().contiguous() for t in tensors)
+    out = torch.empty(pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
+    L.check(L.load().npf_masked_attn_fwd_weighted(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
+                                                  _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks, n_ctx_tasks, n_keys,
+                                                  n_queries, d, float(scale), L.ptr(out), L.stream_ptr()), "npf_masked_attn_fwd_weighted")
+    return out
+
+
+def weighted_mean(R_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, n_ctx_tasks: int, pts: int,
+                  F: int) -> torch.Tensor:
+    """Row-major [n_tasks, pad32(F)]: row ``j`` is the ``w[j]``-weighted mean over the admissible points (below
+    ``n_valid[j % n_ctx_tasks]``, ``0 < w < inf``) of context task ``j % n_ctx_tasks`` of the PT32 tensor ``R_pt``
+    [n_ctx_tasks, pts, F], zeros where the admissible weights sum to 0 (``npf_weighted_mean``: sums and division in double, one
+    rounding, fixed order).  ``w``: float [n_tasks, pts] (or [S, n_ctx_tasks, pts]).  Counts and weights as in
+    :func:`masked_attention_weighted`.  Inference only: a call in which an input requires grad is refused."""
+    if n_ctx_tasks < 1 or n_tasks < 0 or n_tasks % n_ctx_tasks != 0:
+        raise ValueError(f"n_tasks={n_tasks} must be a multiple of n_ctx_tasks={n_ctx_tasks} >= 1 (task j reads context task j % n_ctx_tasks)")
+    if pts < 1 or F < 1:
+        raise ValueError(f"weighted_mean needs pts >= 1 and F >= 1, got {pts}, {F}")
+    if R_pt.requires_grad or (isinstance(w, torch.Tensor) and w.requires_grad):
+        raise RuntimeError("weighted_mean is inference only (no backward pass): detach the inputs")
+    if tuple(R_pt.shape) != tuple(pt_shape(n_ctx_tasks, pts, F)) or R_pt.dtype != torch.float32:
+        raise ValueError(f"R_pt must be an fp32 PT32 tensor of shape {tuple(pt_shape(n_ctx_tasks, pts, F))}, got {R_pt.dtype} {tuple(R_pt.shape)}")
+    w = key_weights_f32(w, n_tasks, pts)
+    n_valid = counts_i32(n_valid, n_ctx_tasks)
+    R_pt = R_pt.detach().contiguous()
+    out = torch.empty((n_tasks, pad32(F)), dtype=torch.float32, device=R_pt.device)  # (written whole)
+    L.check(L.load().npf_weighted_mean(L.ptr(R_pt), L.ptr(w), _iptr(n_valid), n_tasks, n_ctx_tasks, pts, pad32(F), L.ptr(out),
+                                       L.stream_ptr()), "npf_weighted_mean")
+    return out
+
+
 def masked_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
     """Mean over the first ``n_valid[task]`` points of a PT32 tensor -> row-major [n_tasks, pad32(F)] (zeros where a task has none):
     ``torch.mean(R, dim=1)`` (npf/neuralproc/np.py:95, attnnp.py:181) of the batch cut per task; counts as in :func:`masked_attention`."""

@@ -26,12 +26,13 @@ import torch.nn as nn
 from torch.distributions import Independent, Normal
 
 from . import functional as FN
-from .architectures import (MLP, DotAttender, LeaveOneOut, MergeFlatInputs, MultiheadAttender, PrefixTail, SelfAttention,
+from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlatInputs, MultiheadAttender, PrefixTail, SelfAttention,
                             get_attender, merge_flat_input)
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score"]
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Reweighted", "bootstrap_weights",
+           "kfold_weights"]
 
 
 def MultivariateNormalDiag(loc, scale_diag):
@@ -270,6 +271,88 @@ class Conditioned:
                 n = torch.full((self.B,), rows, dtype=torch.int32, device=Xc_pt.t.device)
             return m._loo_from(Xc_pt, R_pts, n, self.B, rows)
 
+    def _rows(self) -> int:
+        """Rows per task of the stored context: ``capacity``, or C."""
+        return self.C if self.capacity is None else self.capacity
+
+    def _row_tensors(self, what):
+        """(encoded context points, per-point representations, live counts or None) of a state that holds the row tensors; the
+        refusals of :meth:`sample_functions` for one that does not."""
+        m = self._model
+        if self.capacity is not None:
+            Xc_pt, R_pts = self._Xc_pt, self._R_pts
+        else:
+            padded_kind = self.n_cntxt is not None and self.C > 0
+            if self._fused_t and not padded_kind:
+                raise ValueError(f"{what}: this context was stored for the fused target side (images of keys / values only); "
+                                 "condition with counts (n_cntxt=...) or a capacity (condition_with_capacity)")
+            if self.C == 0:
+                raise ValueError(f"{what}: no context points")
+            Xc_pt, R_pts = self._Xc_pt, (self._R if m._attentive else self._R_pts)
+        if Xc_pt is None or R_pts is None:
+            raise ValueError(f"{what}: this state does not hold the encoded context points and their representations")
+        return Xc_pt, R_pts, self.n_cntxt
+
+    def reweighted(self, W) -> "Reweighted":
+        """S replicates of the stored context that differ in a non-negative weight per (replicate, task, context point) ->
+        :class:`Reweighted`, whose :meth:`Reweighted.query` predicts from all of them at once.  ``W``: float device tensor
+        [S, B, rows] (rows: ``capacity``, or C), used as given -- not copied if it is contiguous fp32, so weights overwritten in place
+        are seen by a replayed graph.  In replicate ``s`` point ``i`` of task ``b`` counts ``W[s, b, i]`` times: softmax attention
+        takes ``p_k ~ w_k exp(s_k)``, mean pooling ``sum w_k r_k / sum w_k`` (``npf_masked_attn_fwd_weighted`` /
+        ``npf_weighted_mean``).  For integer weights the result is what ``forward`` gives on the context with its rows repeated; a
+        weight of 0 (or a negative, NaN or Inf one) removes the point, and so does a row at or beyond the task's count.  The
+        conditioned state is READ ONLY and stored once: nothing is encoded again, no key or value is copied per replicate.
+        Accepted on the states :meth:`sample_functions` accepts: conditioned with a capacity, with ``n_cntxt``, or without counts if
+        not stored for the fused target side.  Not implemented: ``is_self_attn=True`` and the bf16 compute mode.  No host sync."""
+        m = self._model
+        m._refuse_unimplemented("reweighted")
+        rows = self._rows()
+        if not isinstance(W, torch.Tensor) or not W.is_floating_point():
+            raise ValueError(f"W must be a float device tensor [S, B={self.B}, rows={rows}], got "
+                             f"{W.dtype if isinstance(W, torch.Tensor) else type(W).__name__}")
+        if W.dim() != 3 or W.shape[0] < 1 or tuple(W.shape[1:]) != (self.B, rows):
+            raise ValueError(f"W must be [S >= 1, B={self.B}, rows={rows}] (one weight per replicate, task and stored context row), "
+                             f"got {list(W.shape)}")
+        Xc_pt, R_pts, n = self._row_tensors("reweighted")
+        if W.device != R_pts.t.device:
+            raise ValueError(f"W lives on {W.device}, the conditioned state on {R_pts.t.device}")
+        if W.requires_grad:
+            raise RuntimeError("reweighted is inference only (no gradient flows to the weights): detach W")
+        if n is None:  # (conditioned without counts: every task holds all C rows)
+            n = torch.full((self.B,), rows, dtype=torch.int32, device=W.device)
+        return Reweighted(self, W.to(torch.float32).contiguous(), Xc_pt, R_pts, n, rows)
+
+    def bootstrap(self, X_trgt, n_samples, generator=None) -> HeadDistribution:
+        """``reweighted(bootstrap_weights(n_cntxt, n_samples, rows, generator)).query(X_trgt)``: the predictions of ``n_samples``
+        resamplings of every task's context points with replacement -> batch shape [n_z, n_samples * B, T], replicate-major.  Their
+        spread is how much the prediction depends on which points happened to be observed."""
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError(f"n_samples must be at least 1, got {n_samples}")
+        self._model._refuse_unimplemented("reweighted")
+        rows = self._rows()
+        _, R_pts, n = self._row_tensors("reweighted")
+        dev = R_pts.t.device
+        n = n if n is not None else torch.full((self.B,), rows, dtype=torch.int32, device=dev)
+        return self.reweighted(bootstrap_weights(n, S, rows, generator=generator, device=dev)).query(X_trgt)
+
+    def kfold(self, folds, k) -> HeadDistribution:
+        """The k-fold predictive of the stored context: for every context point ``i`` of every task, p(y_i | the task's points of
+        the OTHER folds) at ``x_i`` -> :class:`HeadDistribution` with batch shape [1, B, rows] whose target counts are the live
+        context counts -- see :meth:`NeuralProcessFamily.kfold`.  From the stored rows: nothing is encoded again and the state is
+        only read.  Accepted on the states :meth:`reweighted` accepts.  Inference only, no host sync."""
+        m = self._model
+        m._refuse_kfold()
+        rows = self._rows()
+        k = _check_folds(folds, k, self.B, rows)
+        Xc_pt, R_pts, n = self._row_tensors("kfold")
+        if folds.device != R_pts.t.device:
+            raise ValueError(f"folds lives on {folds.device}, the conditioned state on {R_pts.t.device}")
+        with torch.no_grad():
+            if n is None:
+                n = torch.full((self.B,), rows, dtype=torch.int32, device=folds.device)
+            return m._kfold_from(Xc_pt, R_pts, n, folds, k, self.B, rows)
+
     def _function_sampler(self, X_trgt, n_samples, eps, chunk):
         """The argument checks of :meth:`sample_functions` -> (its per-call state, ``eps``, ``chunk``)."""
         m = self._model
@@ -429,6 +512,107 @@ class _FunctionSampler:
                 src += [att._project(Xn_pt.t, SB, n, att.key_transform), att._project(Rn_pts.t, SB, n, att.value_transform)]
         FN.append_points([(s, dst, F) for s, (dst, F) in zip(src, self.tails)], self.n_tail, None, SB, n, self.m_tail)
         return y
+
+
+class Reweighted:
+    """S replicates of one conditioned context that differ in a weight per (replicate, task, context point)
+    (:meth:`Conditioned.reweighted`).  Holds the weights ``W`` [S, B, rows] (the caller's tensor if it was contiguous fp32: overwrite
+    it in place and query again, or replay a captured query) and reads the conditioned state, which stays as it is."""
+
+    def __init__(self, post: "Conditioned", W, Xc_pt, R_pts, n, rows):
+        self.post, self.W, self.S, self.B, self.rows = post, W, W.shape[0], post.B, rows
+        self._Xc_pt, self._R_pts, self.n_cntxt = Xc_pt, R_pts, n
+
+    def _eps(self):
+        """[n_z, S B, 1, z]: every replicate of task b is drawn with the state's eps of task b (the rule of ``sample_functions``)."""
+        post = self.post
+        if post.eps is not None:
+            eps = post.eps
+        else:  # (``condition`` keeps z, not the draw behind it: the same draw, from z = loc + scale * eps)
+            q = post.q_zCc.base_dist
+            eps = (post.z_samples - q.loc) / q.scale
+        return eps.repeat(1, self.S, 1, 1)
+
+    def query(self, X_trgt, n_trgt=None) -> HeadDistribution:
+        """p(y | replicate s of the context, z) at ``X_trgt`` [B, T, x_dim] (shared by the replicates) -> :class:`HeadDistribution`
+        with batch shape [n_z, S * B, T], replicate-major (task ``s * B + b``, the order of ``sample_functions``); ``n_trgt`` [B]:
+        per-task target sizes of a padded grid, repeated per replicate.  CNP: ``npf_weighted_mean``, then the decoder per (replicate,
+        task); AttnCNP: ``npf_masked_attn_fwd_weighted`` over the one stored copy of keys / values, then the decoder of the padded
+        route; LNP / AttnLNP: q(z | replicate) from the weighted mean of the per-point representations and ``z = loc + scale * eps``
+        with the state's ``eps`` of task ``b`` for every replicate (the state's ``n_z`` draws are kept), then merge and decode over
+        the S * B tasks.  A replicate without an admissible point is predicted from the empty context.  ``summary`` and ``score``
+        work on the result as on any other.  Inference only, no host sync: a query and its ``summary`` can be captured in one graph
+        and replayed after ``W`` was overwritten in place."""
+        post, m, S, B, rows = self.post, self.post._model, self.S, self.B, self.rows
+        SB, r = S * B, m.r_dim
+        with torch.no_grad():
+            if n_trgt is not None:
+                n_trgt = m._check_counts(n_trgt, X_trgt, "n_trgt").repeat(S)
+            m._check_tensors(X_trgt)
+            if X_trgt.dim() != 3 or X_trgt.shape[0] != B:
+                raise ValueError(f"X_trgt must be [B={B}, T, x_dim] (the batch the model was conditioned on), got {list(X_trgt.shape)}")
+            T = X_trgt.shape[1]
+            if T == 0:
+                raise ValueError("no target points")
+            Xt_pt = m._xenc_pt(X_trgt)
+            z = Rw = None
+            if post.z_samples is not None or not m._attentive:
+                Rw = FN.weighted_mean(self._R_pts.t, self.W, self.n_cntxt, SB, B, rows, r)[:, :r].reshape(SB, 1, r)
+            if post.z_samples is not None:
+                q = m._latent_dist_from(Rw).base_dist
+                z = q.loc.unsqueeze(0) + q.scale.unsqueeze(0) * self._eps()  # [n_z, S B, 1, z]
+            if m._attentive:
+                # (the decoder, and the residual of a transformer attender, read the encoded targets per task: tiled; the attention
+                # itself reads those of the first replicate)
+                Xt_rep = PTensor(Xt_pt.t.repeat(S, 1, 1, 1, 1), T, m.x_transf_dim) if S > 1 else Xt_pt
+                suff = m._target_suffstat(self._Xc_pt, z, self._R_pts, Xt_rep, SB, rows, T,
+                                          n_valid=KeyWeights(self.W, self.n_cntxt, S), n_q_valid=n_trgt)
+            else:
+                vec = Rw.reshape(SB, r) if z is None else m._rep_rows(z, Rw, SB)
+                suff = m._decode_taskvec(Xt_pt, vec.contiguous(), B, T, vec.shape[0])
+            return m._head(suff, None, SB, T, n_trgt=n_trgt)
+
+
+def bootstrap_weights(n_cntxt_or_C, S, rows, generator=None, device=None, n_tasks=1) -> torch.Tensor:
+    """Bootstrap multiplicities [S, B, rows] (fp32) for :meth:`Conditioned.reweighted`: for every (s, b), ``n[b]`` draws with
+    replacement among the first ``n[b]`` rows -- row ``i`` holds how often it was drawn -- and 0 beyond.  ``n_cntxt_or_C``: the
+    per-task counts, an integer tensor [B] (clamped to [0, rows]; never read by the host), or one host int C for each of ``n_tasks``
+    tasks.  ``generator``: a ``torch.Generator`` of ``device`` (default: the counts' device).  No host sync."""
+    S, rows = int(S), int(rows)
+    if S < 1 or rows < 1:
+        raise ValueError(f"bootstrap_weights needs S >= 1 and rows >= 1, got {S} and {rows}")
+    if isinstance(n_cntxt_or_C, torch.Tensor):
+        n = n_cntxt_or_C
+        if n.dim() != 1 or n.is_floating_point() or n.dtype == torch.bool:
+            raise ValueError(f"the counts must be an integer tensor [B], got {n.dtype} {list(n.shape)}")
+        device = n.device if device is None else torch.device(device)
+        n = n.to(device)
+    else:
+        n = torch.full((int(n_tasks),), int(n_cntxt_or_C), dtype=torch.int32, device=device)
+        device = n.device
+    B = n.shape[0]
+    n = n.clamp(0, rows).view(1, B, 1)
+    u = torch.rand(S, B, rows, generator=generator, device=device)
+    idx = (u * n).long().minimum((n - 1).clamp(min=0).long())  # draw j of (s, b): uniform on the first n[b] rows
+    drawn = (torch.arange(rows, device=device).view(1, 1, rows) < n).to(torch.float32).expand(S, B, rows)  # (the first n[b] draws count)
+    return torch.zeros(S, B, rows, dtype=torch.float32, device=device).scatter_add_(2, idx, drawn.contiguous())
+
+
+def _check_folds(folds, k, B, rows) -> int:
+    k = int(k)
+    if k < 2:
+        raise ValueError(f"k must be at least 2 folds, got {k}")
+    if not isinstance(folds, torch.Tensor) or folds.is_floating_point() or folds.dtype == torch.bool:
+        raise ValueError(f"folds must be an integer tensor [B={B}, rows={rows}] of fold ids in [0, k), got "
+                         f"{folds.dtype if isinstance(folds, torch.Tensor) else type(folds).__name__}")
+    if tuple(folds.shape) != (B, rows):
+        raise ValueError(f"folds must be [B={B}, rows={rows}] (one fold id per stored context row), got {list(folds.shape)}")
+    return k
+
+
+def kfold_weights(folds, k) -> torch.Tensor:
+    """``W[f, b, i] = (folds[b, i] != f)`` as fp32 [k, B, rows]: replicate ``f`` is the context without the points of fold ``f``."""
+    return (folds.unsqueeze(0) != torch.arange(int(k), device=folds.device, dtype=folds.dtype).view(-1, 1, 1)).to(torch.float32)
 
 
 def _mean_rows(R_pt, pts, B, r, n_valid=None):
@@ -616,12 +800,19 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
             if n_z is not None:
                 self.n_z_samples = n_z  # (read by AttnLNP's dispatch rule; ``query`` uses what is stored below, not this attribute)
             fused_t = self._fused_target_side(C, 1)  # (the rule does not depend on the number of targets: x6.target_side_usable)
-            Xc_pt, R = self._context_stage(X_cntxt, Y_cntxt, n_cntxt, fused_t)
+            R_pts = None
+            if not self._attentive and C > 0 and not getattr(self, "is_self_attn", False):
+                # (CNP / LNP: the launches of ``_context_stage`` with the per-point representations kept next to their mean, for
+                # ``Conditioned.reweighted`` / ``kfold``)
+                Xc_pt, R_pts = self._encode_points(X_cntxt, Y_cntxt)
+                R = self._pool_pt(R_pts, B, n_valid=n_cntxt)
+            else:
+                Xc_pt, R = self._context_stage(X_cntxt, Y_cntxt, n_cntxt, fused_t)
             z_samples = q_zCc = None
             if n_z is not None:
                 q_zCc = self._infer_q_zCc(R, B, n_cntxt if C > 0 else None)
                 z_samples = q_zCc.rsample([n_z])
-        return Conditioned(self, Xc_pt, R, z_samples, q_zCc, n_cntxt, B, C, fused_t)
+        return Conditioned(self, Xc_pt, R, z_samples, q_zCc, n_cntxt, B, C, fused_t, R_pts=R_pts)
 
     def condition_with_capacity(self, X_cntxt, Y_cntxt, capacity, n_cntxt=None, n_z_samples=None) -> "Conditioned":
         """:meth:`condition` into a context that can grow: the state is stored at ``capacity`` >= C rows per task (C = 0 is allowed)
@@ -703,6 +894,49 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         """The leave-one-out predictive from the encoded context points and their per-point representations (PTensors of ``rows`` rows
         per task, ``n`` [B] device int32 of them real)."""
         return self._head(self._loo_suffstat(Xc_pt, R_pts, n, B, rows), None, B, rows, n_trgt=n)
+
+    def kfold(self, X_cntxt, Y_cntxt, folds, k, n_cntxt=None) -> HeadDistribution:
+        """The k-fold predictive of a context: for every task ``b`` and context point ``i``, p(y_i | the task's points whose fold id
+        differs from ``folds[b, i]``) at ``x_i`` -- what ``forward`` returns for the context cut to the other folds with ``x_i`` as
+        the only target -- out of ONE encode of the context.  ``folds``: integer device tensor [B, C] of fold ids in [0, k) (ids
+        outside are clamped into it), ``k`` a host int >= 2; contiguous bands of ids give leave-a-band-out.  The k replicates
+        ``W[f, b, i] = (folds[b, i] != f)`` run as one weighted attention launch over the context points as queries
+        (``npf_masked_attn_fwd_weighted``; CNP: one ``npf_weighted_mean``), one device index op picks for point ``i`` the row of
+        replicate ``folds[b, i]``, and the decoder runs once on the gathered [B, C] representations.  -> :class:`HeadDistribution`
+        with batch shape [1, B, C] whose target counts are the context counts, as with :meth:`loo` (``kfold(...).score(Y_cntxt)``
+        gives the k-fold scores); a point whose fold holds every point of its task is predicted from the empty context.  With
+        ``folds[b, i] = i`` and ``k = C`` this is :meth:`loo`.  Inference only, no host sync.  Not implemented: ``is_self_attn=True``,
+        the bf16 compute mode and the latent models."""
+        self._refuse_kfold()
+        if X_cntxt.dim() != 3 or Y_cntxt.dim() != 3 or X_cntxt.shape[:2] != Y_cntxt.shape[:2]:
+            raise ValueError(f"X_cntxt / Y_cntxt must be [B, C, x_dim] / [B, C, y_dim], got {list(X_cntxt.shape)} / {list(Y_cntxt.shape)}")
+        B, C, _ = X_cntxt.shape
+        if C == 0:
+            raise ValueError("kfold: no context points")
+        k = _check_folds(folds, k, B, C)
+        with torch.no_grad():
+            if n_cntxt is not None:
+                n_cntxt = self._check_counts(n_cntxt, X_cntxt, "n_cntxt")
+            self._check_tensors(X_cntxt, Y_cntxt)
+            if folds.device != X_cntxt.device:
+                raise ValueError(f"folds lives on {folds.device}, the batch on {X_cntxt.device}")
+            if n_cntxt is None:
+                n_cntxt = torch.full((B,), C, dtype=torch.int32, device=X_cntxt.device)
+            Xc_pt, R_pts = self._encode_points(X_cntxt, Y_cntxt)
+            return self._kfold_from(Xc_pt, R_pts, n_cntxt, folds, k, B, C)
+
+    def _refuse_kfold(self):
+        if self.encoded_path != "deterministic":
+            raise NotImplementedError("kfold is not implemented for latent models (LNP / AttnLNP): q(z | C without the fold) differs "
+                                      "per fold and the decoder takes one z per task; use Conditioned.reweighted with the fold masks")
+        self._refuse_unimplemented("kfold")
+
+    def _kfold_from(self, Xc_pt, R_pts, n, folds, k, B, rows) -> HeadDistribution:
+        """The k-fold predictive from the encoded context points and their per-point representations (PTensors of ``rows`` rows per
+        task, ``n`` [B] device int32 of them real): the representation of point ``i`` is that of replicate ``folds[b, i]``."""
+        own = folds.long().clamp(0, k - 1)
+        R_g = self._kfold_rep(Xc_pt, R_pts, n, kfold_weights(own, k), own, k, B, rows)
+        return self._head(self._decode_pointwise(R_g, Xc_pt.t, B, rows), None, B, rows, n_trgt=n)
 
     def _decode_pointwise(self, R_t, X1_pt, B, T):
         """The decoder on one representation per target (PT32 ``R_t`` [B, T, r]) as the padded route of the attentive models runs it."""
@@ -1022,6 +1256,13 @@ class CNP(NeuralProcessFamily):
         ``encode_globally`` at C = 0)."""
         return self._decode_pointwise(FN.loo_mean(R_pts.t, n, B, rows, self.r_dim), Xc_pt.t, B, rows)
 
+    def _kfold_rep(self, Xc_pt, R_pts, n, W, own, k, B, rows):
+        """PT32 [B, rows, r]: row ``i`` is the mean over the task's points outside fold ``own[b, i]`` -- the k weighted means per
+        task, then one index op (zeros where no point is left, as ``encode_globally`` at C = 0)."""
+        r = self.r_dim
+        means = FN.weighted_mean(R_pts.t, W, n, k * B, B, rows, r)[:, :r].view(k, B, r)
+        return FN.pack_pt(means[own, torch.arange(B, device=own.device).view(B, 1)])
+
 
 class LNP(LatentNeuralProcessFamily, CNP):
     """(Latent) neural process (npf/neuralproc/np.py:113-163)."""
@@ -1130,6 +1371,9 @@ class AttnCNP(NeuralProcessFamily):
         elif isinstance(n_valid, LeaveOneOut):  # (the targets are the context points: a task needs two of them to have a key left)
             R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
             live = n_valid.n_valid > 1
+        elif isinstance(n_valid, KeyWeights):  # (B = S replicates x the stored tasks: a replicate needs one key of positive weight)
+            R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
+            live = n_valid.live(B)
         else:
             R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
             live = n_valid > 0
@@ -1140,6 +1384,18 @@ class AttnCNP(NeuralProcessFamily):
     def _loo_suffstat(self, Xc_pt, R_pts, n, B, rows):
         """The padded route with the encoded context points as targets and the diagonal of the attention excluded."""
         return self._target_suffstat(Xc_pt, None, R_pts, Xc_pt, B, rows, rows, n_valid=LeaveOneOut(n), n_q_valid=n)
+
+    def _kfold_rep(self, Xc_pt, R_pts, n, W, own, k, B, rows):
+        """PT32 [B, rows, r]: row ``i`` is the attention of context point ``i`` over the task's points outside fold ``own[b, i]`` --
+        the padded route over k * B replicate tasks with the encoded context points as queries, then one index op over the
+        replicates (whole PT32 tiles: the rows beyond ``rows`` take replicate 0's zeros)."""
+        Xq = PTensor(Xc_pt.t.repeat(k, 1, 1, 1, 1), rows, self.x_transf_dim)
+        R_t = self._attend_padded(Xc_pt, R_pts, Xq, k * B, rows, rows, KeyWeights(W, n, k), n_q_valid=n.repeat(k))
+        tiles = R_t.shape[1]
+        idx = torch.zeros(B, tiles * 32, dtype=torch.long, device=own.device)
+        idx[:, :rows] = own
+        idx = idx.view(1, B, tiles, 1, 32, 1).expand(1, B, tiles, R_t.shape[2], 32, 4)
+        return torch.gather(R_t.view(k, B, *R_t.shape[1:]), 0, idx)[0]
 
     def _attend_into(self, ch, Xc_pt, R, Xt_pt, C, T, tap_x1: bool = False):
         """cur of ``ch`` <- attention of the targets over the context (attnnp.py:118-131): fused into
