@@ -20,6 +20,8 @@
  *   npf_masked_gauss_head_fwd/bwd  the same over a batch of padded targets whose per-task sizes are device data
  *   npf_mixture_summary  mean / std / quantiles of the predictive mixture over the latent samples (inference; no reference counterpart)
  *   npf_mixture_score    log density / PIT / CRPS of an observation under that mixture (inference; no reference counterpart)
+ *   npf_waveform_match   overlap / match / mismatch of predicted against reference waveforms over a time-shift grid (inference; no
+ *                        reference counterpart)
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -629,6 +631,43 @@ typedef struct npf_append_pair {
 } npf_append_pair_t;
 int npf_append_points(const npf_append_pair_t *pairs, int32_t n_pairs, int32_t *n_valid, const int32_t *n_new, int32_t n_tasks,
                       int32_t n_rows, int32_t capacity, void *stream);
+
+/* ---- waveform match over a time-shift grid (csrc/waveform_kernels.hip; inference, no reference counterpart) -----------------------
+ * Row r = k * n_tasks + b (latent sample k, task b) of h holds the predicted waveform h_t = A_t e^{i phi_t}: A = h[r][t][0],
+ * phi = h[r][t][1], h_ld >= 2 floats per point (2: a [n_rows][pts][2] tensor; 4: the raw decoder output of a dy = 2 head, whose first
+ * two entries are the head's loc).  g[n_tasks][pts][2] holds the reference g_t = A'_t e^{i phi'_t} of every task, wgt the weight
+ * w_t of every point (the caller's 4 df / S_n(f); NULL: all ones) and freq its physical frequency f_t, either as one row shared by
+ * the tasks (wgt_rows / freq_rows = 1) or one per task (= n_tasks).  Over the uniform grid tau_j = tau0 + j dtau, j < n_tau:
+ *   hh  = sum_t w_t A_t^2            gg = sum_t w_t A'_t^2
+ *   c_j = sum_t w_t A_t A'_t exp(i (phi_t - phi'_t + 2 pi f_t tau_j))
+ *   c_0/ = the same sum without the 2 pi f tau term (no time shift, whatever the grid is)
+ *   overlap  = Re c_0/ / sqrt(hh gg)
+ *   match    = max_j |c_j| / sqrt(hh gg)        tau_index = the smallest j that attains it
+ *   phase    = arg c_{tau_index}
+ *   mismatch = 1 - match                        (formed in double, then rounded once)
+ * n_tau == 0 (no time maximisation): match = |c_0/| / sqrt(hh gg), phase = arg c_0/, tau_index = 0, and freq is not read (may be
+ * NULL).  A point is removed unless 0 < w_t < +inf (the admissibility rule of npf_masked_attn_fwd_weighted): A, phi, A', phi', f of
+ * a removed point have no influence, NaN included.  n_valid: NULL or a DEVICE int32 [n_tasks] tensor (clamped to [0, pts]): task b
+ * owns its first n_valid[b] points, nothing at or beyond is read.  A row with hh gg == 0 (or no point left) gets overlap = match = 0,
+ * mismatch = 1, tau_index = 0, phase = 0 and zeros in corr.
+ * Arithmetic: everything -- the phase, its sine and cosine, the products and the sums -- is double, the inputs are fp32 values widened
+ * exactly and every output is rounded to fp32 once.  Launch 1: one workgroup per (row, chunk of NPF_WAVEFORM_JC shifts); per point one
+ * sincos at the chunk's first shift and one of the step 2 pi f dtau, then a complex rotation per shift (the recurrence restarts at
+ * every chunk); sums reduced in a fixed order into `workspace`.  Launch 2: per row the normalisation, maximum and outputs.  No atomics:
+ * a second call on the same inputs gives the same bits.  The host reads neither the counts nor the data: the call sits in a captured
+ * graph.  Outputs (each may be NULL, at least one must be given; every requested element is written): hh[n_rows], gg[n_tasks],
+ * overlap / match / mismatch / tau_index / phase [n_rows], corr[n_rows][max(n_tau, 1)][2] = c_j / sqrt(hh gg) (n_tau == 0: c_0/).
+ * workspace: npf_waveform_match_workspace_bytes(n_rows, n_tau) bytes of device memory, 8-byte aligned (NPF_EINVAL (-1) from that
+ * function for n_rows <= 0 or n_tau outside [0, 65536]).
+ * Status: NPF_EINVAL (nothing launched) for n_rows % n_tasks != 0, h_ld < 2, wgt_rows / freq_rows of a given pointer not in
+ * {1, n_tasks}, n_tau < 0, n_tau > 65536, n_tau > 0 with freq == NULL, all outputs NULL, a NULL h, g or workspace, pts <= 0,
+ * n_tasks <= 0, n_rows <= 0 or n_rows > 2^24. */
+#define NPF_WAVEFORM_JC 16
+int64_t npf_waveform_match_workspace_bytes(int32_t n_rows, int32_t n_tau);
+int npf_waveform_match(const float *h, int32_t h_ld, const float *g, const float *wgt, int32_t wgt_rows, const float *freq,
+                       int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                       double dtau, int32_t n_tau, float *hh, float *gg, float *overlap, float *match, float *mismatch,
+                       int32_t *tau_index, float *phase, float *corr, void *workspace, void *stream);
 
 int npf_version(void);
 

@@ -145,6 +145,9 @@ SIGNATURES = {
     "npf_masked_mean_fwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "npf_masked_mean_bwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _i32, _p]),
     "npf_append_points": (C.c_int, [C.POINTER(NpfAppendPair), _i32, _p, _p, _i32, _i32, _i32, _p]),
+    "npf_waveform_match_workspace_bytes": (_i64, [_i32, _i32]),
+    "npf_waveform_match": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
+                                     _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "npf_version": (C.c_int, []),
 }
 

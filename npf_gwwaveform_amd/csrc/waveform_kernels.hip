@@ -1,0 +1,191 @@
+// Match of predicted waveforms h_t = A_t e^{i phi_t} against reference waveforms g_t = A'_t e^{i phi'_t} over a uniform grid of time
+// shifts tau_j = tau0 + j dtau (npf_waveform_match): the noise-weighted complex correlation
+//   c_j = sum_t w_t A_t A'_t exp(i (phi_t - phi'_t + 2 pi f_t tau_j)),   hh = sum_t w_t A_t^2,   gg = sum_t w_t A'_t^2,
+// c_0/ the same sum without the time-shift term, and per row overlap = Re c_0/ / sqrt(hh gg), match = max_j |c_j| / sqrt(hh gg) with
+// the first index that attains it, phase = arg c there and mismatch = 1 - match.  A pure reduction, in DOUBLE throughout: useful
+// mismatches are 1e-4 .. 1e-8 and the phases reach thousands of radians, where fp32 sines and sums are worth 1e-8 of the match.
+// The inputs are fp32 values widened exactly; every output is rounded to fp32 once.
+//
+// Launch 1 (waveform_corr_kernel): one workgroup per (row, chunk of JC time shifts).  A thread strides over the points; per point it
+// forms z = a_t e^{i (theta_t + 2 pi f_t tau_j0)} at the chunk's first shift and the step s = e^{i 2 pi f_t dtau} with one double
+// sincos each and advances z <- z s through the chunk: four FMAs per (t, j), no sine in the inner loop, and the recurrence restarts
+// from a direct sincos at every chunk, so it never runs longer than JC steps.  The 2 JC sums live in registers and are reduced in a
+// fixed order (wave shuffles, then LDS across the waves) into the double workspace; the chunk-0 workgroup adds hh, gg and c_0/.
+// Launch 2 (waveform_finish_kernel): one wavefront per row normalises, takes the maximum with the smallest index and writes the
+// outputs.  No atomics anywhere: a second call on the same inputs gives the same bits.
+//
+// Workspace, doubles, per row: [hh, gg, Re c_0/, Im c_0/, (Re c_j, Im c_j) for j < JC * chunks].
+#include "npf_common.hpp"
+
+namespace npf {
+
+constexpr int kWfJC = NPF_WAVEFORM_JC;  // time shifts per workgroup of launch 1
+constexpr int kWfThreads = 128;
+constexpr int kWfMaxTau = 65536;
+constexpr double kWfTwoPi = 6.283185307179586476925286766559;
+
+inline int wf_chunks(int n_tau) { return n_tau > 0 ? (n_tau + kWfJC - 1) / kWfJC : 1; }
+inline int64_t wf_row_doubles(int n_tau) { return 4 + 2 * (int64_t)kWfJC * wf_chunks(n_tau); }
+
+// dst[i] = sum over the workgroup of v[i], i < N (N <= THREADS): lanes by xor shuffles, then the waves in order.  red: N * waves doubles.
+template <int N, int THREADS>
+__device__ __forceinline__ void block_sum_store(double (&v)[N], double* red, double* __restrict__ dst) {
+  constexpr int WAVES = THREADS / 64;
+  static_assert(N <= THREADS, "one thread per sum");
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
+  }
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();  // red may still be read by a previous call
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[i * WAVES + wave] = v[i];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < N) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) s += red[threadIdx.x * WAVES + w];
+    dst[threadIdx.x] = s;
+  }
+}
+
+template <int JC, int THREADS>
+__global__ __launch_bounds__(THREADS) void waveform_corr_kernel(const float* __restrict__ h, int h_ld, const float* __restrict__ g,
+                                                                 const float* __restrict__ wgt, int wgt_per_task,
+                                                                 const float* __restrict__ freq, int freq_per_task,
+                                                                 const int32_t* __restrict__ n_valid, int n_tasks, int pts, double tau0,
+                                                                 double dtau, int n_tau, double* __restrict__ ws, int64_t row_doubles) {
+  __shared__ double red[2 * JC * (THREADS / 64)];
+  const int r = blockIdx.x, chunk = blockIdx.y, b = r % n_tasks;
+  const int nv = n_valid ? clamp_count(n_valid, b, pts) : pts;
+  const float* hr = h + (size_t)r * (size_t)pts * (size_t)h_ld;
+  const float* gr = g + (size_t)b * (size_t)pts * 2;
+  const float* wr = wgt ? wgt + (wgt_per_task ? (size_t)b * (size_t)pts : 0) : nullptr;
+  const float* fr = n_tau > 0 ? freq + (freq_per_task ? (size_t)b * (size_t)pts : 0) : nullptr;  // (n_tau == 0: freq is not read)
+  const double tau_c = tau0 + (double)(chunk * JC) * dtau;  // the chunk's first shift
+  const bool first = chunk == 0;
+
+  double acc[2 * JC];  // (Re, Im) of c_j, j = chunk * JC + 0 .. JC - 1
+#pragma unroll
+  for (int i = 0; i < 2 * JC; ++i) acc[i] = 0.0;
+  double base[4] = {0.0, 0.0, 0.0, 0.0};  // hh, gg, Re c_0/, Im c_0/ (chunk 0 only)
+
+  for (int t = threadIdx.x; t < nv; t += THREADS) {
+    const float wf = wr ? wr[t] : 1.f;
+    if (!(wf > 0.f && wf < INFINITY)) continue;  // a removed point: nothing else of it is read
+    const double w = (double)wf;
+    const double A = (double)hr[(size_t)t * h_ld], ph = (double)hr[(size_t)t * h_ld + 1];
+    const double Ag = (double)gr[2 * (size_t)t], phg = (double)gr[2 * (size_t)t + 1];
+    const double wa = w * A, a = wa * Ag, theta = ph - phg;
+    if (first) {
+      double sn, cs;
+      sincos(theta, &sn, &cs);
+      base[0] += wa * A;
+      base[1] += (w * Ag) * Ag;
+      base[2] += a * cs;
+      base[3] += a * sn;
+    }
+    if (n_tau > 0) {
+      const double om = kWfTwoPi * (double)fr[t];
+      double sn, cs, ssn, scs;
+      sincos(theta + om * tau_c, &sn, &cs);
+      sincos(om * dtau, &ssn, &scs);
+      double zr = a * cs, zi = a * sn;
+#pragma unroll
+      for (int j = 0; j < JC; ++j) {
+        acc[2 * j] += zr;
+        acc[2 * j + 1] += zi;
+        const double nr = zr * scs - zi * ssn;
+        zi = zr * ssn + zi * scs;
+        zr = nr;
+      }
+    }
+  }
+
+  double* row = ws + (size_t)r * (size_t)row_doubles;
+  if (n_tau > 0) block_sum_store<2 * JC, THREADS>(acc, red, row + 4 + 2 * JC * chunk);
+  if (first) block_sum_store<4, THREADS>(base, red, row);
+}
+
+// One wavefront per row: the maximum of |c_j|^2 with the smallest index that attains it, then the outputs.
+__global__ __launch_bounds__(64) void waveform_finish_kernel(const double* __restrict__ ws, int64_t row_doubles, int n_tasks, int n_tau,
+                                                              float* __restrict__ hh, float* __restrict__ gg, float* __restrict__ overlap,
+                                                              float* __restrict__ match, float* __restrict__ mismatch,
+                                                              int32_t* __restrict__ tau_index, float* __restrict__ phase,
+                                                              float* __restrict__ corr) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const double* row = ws + (size_t)r * (size_t)row_doubles;
+  const double vhh = row[0], vgg = row[1], prod = vhh * vgg;
+  const bool degenerate = prod == 0.0;  // (no point left: both sums are empty)
+  const double nrm = sqrt(prod);
+  const int n = n_tau > 0 ? n_tau : 1;
+  const double* c = n_tau > 0 ? row + 4 : row + 2;  // (no time maximisation: the one candidate is c_0/)
+
+  double best = -1.0;
+  int best_j = 0;
+  for (int j = lane; j < n; j += 64) {
+    const double re = c[2 * j], im = c[2 * j + 1], m2 = re * re + im * im;
+    if (m2 > best) {  // (j ascends: the smallest index of the lane stays)
+      best = m2;
+      best_j = j;
+    }
+    if (corr) {
+      float* o = corr + ((size_t)r * (size_t)n + (size_t)j) * 2;
+      o[0] = degenerate ? 0.f : (float)(re / nrm);
+      o[1] = degenerate ? 0.f : (float)(im / nrm);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double ob = __shfl_xor(best, off);
+    const int oj = __shfl_xor(best_j, off);
+    if (ob > best || (ob == best && oj < best_j)) {
+      best = ob;
+      best_j = oj;
+    }
+  }
+  if (lane != 0) return;
+  if (hh) hh[r] = (float)vhh;
+  if (gg && r < n_tasks) gg[r] = (float)vgg;  // (row r < n_tasks is latent sample 0 of task r)
+  const double re = c[2 * best_j], im = c[2 * best_j + 1];
+  const double m = degenerate ? 0.0 : sqrt(re * re + im * im) / nrm;
+  if (overlap) overlap[r] = degenerate ? 0.f : (float)(row[2] / nrm);
+  if (match) match[r] = (float)m;
+  if (mismatch) mismatch[r] = (float)(1.0 - m);
+  if (tau_index) tau_index[r] = degenerate ? 0 : best_j;
+  if (phase) phase[r] = degenerate ? 0.f : (float)atan2(im, re);
+}
+
+}  // namespace npf
+
+extern "C" int64_t npf_waveform_match_workspace_bytes(int32_t n_rows, int32_t n_tau) {
+  using namespace npf;
+  if (n_rows <= 0 || n_tau < 0 || n_tau > kWfMaxTau) return NPF_EINVAL;
+  return (int64_t)n_rows * wf_row_doubles(n_tau) * (int64_t)sizeof(double);
+}
+
+extern "C" int npf_waveform_match(const float* h, int32_t h_ld, const float* g, const float* wgt, int32_t wgt_rows, const float* freq,
+                                  int32_t freq_rows, const int32_t* n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                                  double dtau, int32_t n_tau, float* hh, float* gg, float* overlap, float* match, float* mismatch,
+                                  int32_t* tau_index, float* phase, float* corr, void* workspace, void* stream) {
+  using namespace npf;
+  if (!h || !g || !workspace || h_ld < 2 || n_tasks <= 0 || n_rows <= 0 || n_rows > (1 << 24) || n_rows % n_tasks != 0 || pts <= 0)
+    return NPF_EINVAL;
+  if (n_tau < 0 || n_tau > kWfMaxTau || (n_tau > 0 && !freq)) return NPF_EINVAL;
+  if (wgt && wgt_rows != 1 && wgt_rows != n_tasks) return NPF_EINVAL;
+  if (freq && freq_rows != 1 && freq_rows != n_tasks) return NPF_EINVAL;
+  if (!hh && !gg && !overlap && !match && !mismatch && !tau_index && !phase && !corr) return NPF_EINVAL;
+  const int64_t row_doubles = wf_row_doubles(n_tau);
+  double* ws = (double*)workspace;
+  hipLaunchKernelGGL((waveform_corr_kernel<kWfJC, kWfThreads>), dim3(n_rows, wf_chunks(n_tau)), dim3(kWfThreads), 0, (hipStream_t)stream,
+                     h, h_ld, g, wgt, (int)(wgt_rows != 1), freq, (int)(freq_rows != 1), n_valid, n_tasks, pts, tau0, dtau, n_tau, ws,
+                     row_doubles);
+  NPF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(waveform_finish_kernel, dim3(n_rows), dim3(64), 0, (hipStream_t)stream, ws, row_doubles, n_tasks, n_tau, hh, gg,
+                     overlap, match, mismatch, tau_index, phase, corr);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}

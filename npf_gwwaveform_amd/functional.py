@@ -3,8 +3,9 @@ points of a task, and the Gaussian head.  Every function launches HIP kernels th
 C ABI (``_lib``); none has a CPU path."""
 from __future__ import annotations
 
+import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -276,6 +277,131 @@ def mixture_score(suff: torch.Tensor, Y: torch.Tensor, n_z: int, dy: int, homosk
                                        int(homoskedastic), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.stream_ptr()),
             "npf_mixture_score")
     return tuple(out)
+
+
+# ---- waveform match over a time-shift grid (csrc/waveform_kernels.hip) ----------------------
+MATCH_NAMES = ("hh", "gg", "overlap", "match", "mismatch", "tau_index", "phase")
+MATCH_JC = 16            # time shifts per workgroup of the correlation launch (NPF_WAVEFORM_JC)
+MATCH_MAX_TAU = 65536    # longest time-shift grid
+_MATCH_WS = {}           # device index -> [float64 workspaces], the last one in use; grown ones are kept (a captured graph holds them)
+
+
+class WaveformMatch(NamedTuple):
+    """What :func:`waveform_match` returns; the entries that were not asked for are ``None``."""
+    hh: Optional[torch.Tensor]         # [R] sum_t w A^2
+    gg: Optional[torch.Tensor]         # [B] sum_t w A'^2
+    overlap: Optional[torch.Tensor]    # [R]
+    match: Optional[torch.Tensor]      # [R]
+    mismatch: Optional[torch.Tensor]   # [R]
+    tau_index: Optional[torch.Tensor]  # [R] int32
+    phase: Optional[torch.Tensor]      # [R]
+    corr: Optional[torch.Tensor]       # [R, max(n_tau, 1), 2]
+
+
+def check_match_want(want) -> tuple:
+    """``want`` as a tuple of names out of ``MATCH_NAMES`` (may be empty: ``corr`` alone); anything else is a ValueError."""
+    if isinstance(want, str) or not isinstance(want, (tuple, list)):
+        raise ValueError(f"want must be a tuple / list of names out of {MATCH_NAMES}, got {want!r}")
+    for w in want:
+        if w not in MATCH_NAMES:
+            raise ValueError(f"want: unknown entry {w!r} (known: {MATCH_NAMES})")
+    return tuple(want)
+
+
+def check_match_args(h_shape, g, weights=None, freqs=None, taus=None):
+    """The shapes and host values of a :func:`waveform_match` call -> ``(R, T, h_ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau)``;
+    ``ValueError`` for anything that does not fit.  Reads shapes only, so it runs on tensors of any device: ``h_shape`` = [R, T, >= 2],
+    ``g`` [B, T, 2] with ``R % B == 0``, ``weights`` / ``freqs`` ``None``, [T] or [B, T], ``taus`` ``None`` or a host triple
+    ``(tau0, dtau, n_tau)`` of two finite floats and ``1 <= n_tau <= MATCH_MAX_TAU``, which needs ``freqs``."""
+    h_shape = tuple(h_shape)
+    if len(h_shape) != 3 or h_shape[2] < 2 or h_shape[0] < 1 or h_shape[1] < 1:
+        raise ValueError(f"h must have shape [R, T, >= 2] (amplitude, phase first), got {list(h_shape)}")
+    R, T, ld = h_shape
+    if not isinstance(g, torch.Tensor) or g.dim() != 3 or g.shape[0] < 1 or tuple(g.shape[1:]) != (T, 2):
+        raise ValueError(f"g (the reference waveforms) must have shape [B, T={T}, 2], got "
+                         f"{list(g.shape) if isinstance(g, torch.Tensor) else type(g).__name__}")
+    B = g.shape[0]
+    if R % B != 0:
+        raise ValueError(f"h holds {R} rows, g {B} tasks: R % B != 0 (row k * B + b is latent sample k of task b)")
+
+    def rows_of(t, what):
+        if t is None:
+            return 1
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) not in ((T,), (B, T)):
+            raise ValueError(f"{what} must be None or a tensor of shape [T={T}] or [B={B}, T={T}], got "
+                             f"{list(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        return 1 if t.dim() == 1 else B
+
+    wgt_rows, freq_rows = rows_of(weights, "weights"), rows_of(freqs, "freqs")
+    tau0, dtau, n_tau = 0.0, 0.0, 0
+    if taus is not None:
+        if isinstance(taus, torch.Tensor) or not isinstance(taus, (tuple, list)) or len(taus) != 3:
+            raise ValueError(f"taus must be None or a host triple (tau0, dtau, n_tau), got {taus!r}")
+        if freqs is None:
+            raise ValueError("taus (a time-shift grid) needs freqs, the physical frequency of every point")
+        t0, dt, n = taus
+        if any(isinstance(v, (torch.Tensor, bool)) or not isinstance(v, (int, float)) for v in (t0, dt)) \
+                or isinstance(n, bool) or not isinstance(n, int):
+            raise ValueError(f"taus = (tau0, dtau, n_tau) takes two host floats and a host int, got {taus!r}")
+        if n < 1 or n > MATCH_MAX_TAU:
+            raise ValueError(f"taus: n_tau must lie in [1, {MATCH_MAX_TAU}], got {n} (no time maximisation: taus=None)")
+        tau0, dtau, n_tau = float(t0), float(dt), n
+        if not (math.isfinite(tau0) and math.isfinite(dtau)):
+            raise ValueError(f"taus: tau0 and dtau must be finite, got {tau0}, {dtau}")
+    return R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau
+
+
+def _match_workspace(device: torch.device, n_bytes: int) -> torch.Tensor:
+    """The float64 workspace of the device, at least ``n_bytes`` long.  It grows outside graph capture only, and a workspace it
+    outgrows is kept: a graph captured earlier still writes to it.  One workspace per device: calls from several streams of one
+    device must be ordered by the caller."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    held = _MATCH_WS.setdefault(idx, [])
+    need = (n_bytes + 7) // 8
+    if not held or held[-1].numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("waveform_match: the workspace has to grow, which cannot happen during graph capture; call once at "
+                               "these sizes before capturing")
+        held.append(torch.empty((max(need, 2 * held[-1].numel() if held else 0),), dtype=torch.float64, device=device))
+    return held[-1]
+
+
+def waveform_match(h: torch.Tensor, g: torch.Tensor, weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None,
+                   taus=None, n_valid: Optional[torch.Tensor] = None, want=MATCH_NAMES, corr: bool = False) -> WaveformMatch:
+    """Overlap, match and mismatch of the predicted waveforms ``h`` [R, T, >= 2] (amplitude ``h[..., 0]``, phase ``h[..., 1]``; any
+    contiguous fp32 device tensor, e.g. the raw decoder output of a ``dy = 2`` head) against the reference waveforms ``g`` [B, T, 2],
+    row ``k * B + b`` of ``h`` against task ``b``: the weighted complex correlation ``c_j = sum_t w A A' exp(i (phi - phi' + 2 pi f
+    tau_j))`` over the uniform grid ``tau_j = tau0 + j dtau`` of ``taus = (tau0, dtau, n_tau)``, normalised by ``sqrt(hh gg)``;
+    ``match = max_j |c_j|`` with ``tau_index`` the first index that attains it and ``phase = arg c`` there, ``overlap`` the real part
+    without time shift, ``mismatch = 1 - match`` formed in double (``include/npf_hip.h`` has the formulae and the edge cases).
+    ``taus=None``: no time maximisation (``match = |c|`` without shift, ``tau_index = 0``).  ``weights`` (``4 df / S_n(f)``; ``None``:
+    ones) and ``freqs`` (Hz): [T], shared by the tasks, or [B, T]; a point whose weight is not in (0, inf) is removed, whatever the
+    other tensors hold there.  ``n_valid``: device integer tensor [B], the real points of every task.  ``want``: the names out of
+    ``MATCH_NAMES`` to compute; ``corr=True`` adds the normalised correlation over the whole grid [R, max(n_tau, 1), 2].  Two
+    ``npf_waveform_match`` launches in double arithmetic, inference only (no autograd), no host sync, deterministic; the workspace
+    is cached per device."""
+    want = check_match_want(want)
+    R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau = check_match_args(getattr(h, "shape", ()), g, weights, freqs, taus)
+    if not want and not corr:
+        raise ValueError(f"want must name at least one of {MATCH_NAMES} (or corr=True)")
+    for t in (h, g, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    h, g = h.detach().contiguous(), g.detach().contiguous()
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and n_tau > 0 else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    lib = L.load()
+    ws = _match_workspace(h.device, int(lib.npf_waveform_match_workspace_bytes(R, n_tau)))
+    new = lambda n, dtype=torch.float32: torch.empty((n,), dtype=dtype, device=h.device)  # noqa: E731
+    out = {name: (new(B if name == "gg" else R, torch.int32 if name == "tau_index" else torch.float32) if name in want else None)
+           for name in MATCH_NAMES}
+    c = torch.empty((R, max(n_tau, 1), 2), dtype=torch.float32, device=h.device) if corr else None
+    L.check(lib.npf_waveform_match(L.ptr(h), ld, L.ptr(g), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows,
+                                   _iptr(nv) if nv is not None else None, R, B, T, tau0, dtau, n_tau,
+                                   *(out[name].data_ptr() if out[name] is not None else None for name in MATCH_NAMES),
+                                   L.ptr(c), ws.data_ptr(), L.stream_ptr()), "npf_waveform_match")
+    return WaveformMatch(*(out[name] for name in MATCH_NAMES), c)
 
 
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------

@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlat
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Reweighted", "bootstrap_weights",
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "Reweighted", "bootstrap_weights",
            "kfold_weights"]
 
 
@@ -57,6 +57,18 @@ class Score(NamedTuple):
     log_density: Optional[torch.Tensor]  # [B, T, y_dim] log of the predictive density at y
     pit: Optional[torch.Tensor]          # [B, T, y_dim] predictive CDF at y (probability integral transform)
     crps: Optional[torch.Tensor]         # [B, T, y_dim] continuous ranked probability score
+
+
+class Match(NamedTuple):
+    """Match of predicted waveforms against reference waveforms (:meth:`HeadDistribution.match`), one entry per (latent sample,
+    task): [n_z, B] for ``of="samples"``, [1, B] for ``of="mean"``; the entries that were not computed are ``None``."""
+    overlap: torch.Tensor              # Re <h, g> / sqrt(<h, h> <g, g>): no phase or time maximisation
+    match: torch.Tensor                # max over the constant phase and the time-shift grid
+    mismatch: torch.Tensor             # 1 - match, formed in double
+    tau: Optional[torch.Tensor]        # float64: the grid time that attains the match (``taus`` given)
+    tau_index: Optional[torch.Tensor]  # int32: its index on the grid, the smallest one (``taus`` given)
+    phase: torch.Tensor                # arg of the correlation there
+    corr: Optional[torch.Tensor]       # [.., B, max(n_tau, 1), 2] normalised correlation over the whole grid (``corr=True``)
 
 
 class HeadDistribution(Independent):
@@ -122,6 +134,38 @@ class HeadDistribution(Independent):
         want = FN.check_want(want)
         n_z = self.batch_shape[0]
         return Score(*FN.mixture_score(self._suff, Y_trgt, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt, want=want))
+
+    def match(self, Y_ref, weights=None, freqs=None, taus=None, of="samples", corr=False) -> Match:
+        """The match of the predicted waveforms against the reference waveforms ``Y_ref`` [B, T, 2] -> :class:`Match`, for a model
+        whose two outputs are (amplitude, phase): the waveform is ``A e^{i phi}``, the match the noise-weighted complex inner product
+        ``sum_t w A A' exp(i (phi - phi'))`` normalised by both norms and maximised over a constant phase and, with ``taus =
+        (tau0, dtau, n_tau)``, over the time shifts ``tau0 + j dtau`` (``freqs``, the physical frequency of every point in Hz, then
+        carries the shift: ``2 pi f tau``); ``mismatch = 1 - match`` is formed in double, so values of 1e-8 survive.  ``weights``: the
+        caller's ``4 df / S_n(f)`` per point ([T] or [B, T]; ``None``: ones); a point whose weight is not in (0, inf) is removed.
+        ``of="samples"``: one entry per latent sample and task, [n_z, B] -- for a latent model the distribution of the mismatch over
+        the sampled functions -- computed on the raw decoder output (``loc`` / ``scale`` are not materialised, ``base_dist`` is
+        left alone).  ``of="mean"``: the match of the mixture-mean amplitude and phase (one moments-only ``npf_mixture_summary``
+        launch), [1, B].  Padded targets (``n_trgt``) are left out.  ``corr=True`` adds the normalised correlation over the whole
+        grid.  Two ``npf_waveform_match`` launches in double arithmetic; inference only, no host sync, so a ``query`` and its
+        ``match`` can be captured in one graph (call once at the sizes before capturing: the workspace is allocated then)."""
+        if self._y_dim != 2:
+            raise ValueError(f"match needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_match_args((rows, T, ld), Y_ref, weights, freqs, taus)
+        if of == "samples":
+            h = self._suff.detach().reshape(rows, T, ld)
+        else:
+            h = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt)[0]
+        want = ("overlap", "match", "mismatch", "phase") + (("tau_index",) if taus is not None else ())
+        m = FN.waveform_match(h, Y_ref, weights, freqs, taus, n_valid=self._n_trgt, want=want, corr=corr)
+        lead = (rows // B, B)
+        tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
+        return Match(m.overlap.view(lead), m.match.view(lead), m.mismatch.view(lead), tau,
+                     m.tau_index.view(lead) if taus is not None else None, m.phase.view(lead),
+                     m.corr.view(*lead, *m.corr.shape[1:]) if corr else None)
 
 
 class Conditioned:
