@@ -13,6 +13,7 @@
 // operand of the second contraction's k-chunk {keys 4 g + j} (a sum over keys does not care about their order).
 // The backward pass recomputes the probabilities from the saved log-sum-exp (one float per head and query) in both layouts:
 // transposed for dQ, plain for dK / dV, which a workgroup owning one (task, head) accumulates over all its queries in registers.
+// D = rowsum(dO * O) is summed on the matrix unit in the order of dO V^T, so dS = P (dO V^T - D) cancels without a residue.
 #include "npf_common.hpp"
 
 namespace npf {
@@ -159,16 +160,22 @@ __global__ __launch_bounds__(256) void mha_bwd_kernel(const float* __restrict__ 
     const int q = q0 + c;
     const bool live = q < T;
     // operands with (lane % 16 -> query, lane / 16 -> feature within the k-chunk): Q, dO, O at [q][4 kc + g]
-    float Qq[NKC], Gq[NKC];
-    float dsum = 0.f;
+    float Qq[NKC], Gq[NKC], Oq[NKC];
 #pragma unroll
     for (int kc = 0; kc < NKC; ++kc) {
       const size_t at = mha_pt(b, tilesT, Fp, live ? q : 0, kMhaD * h + 4 * kc) + g;
       Qq[kc] = live ? Q[at] : 0.f;
       Gq[kc] = live ? dO[at] : 0.f;
-      dsum = fmaf(Gq[kc], live ? O[at] : 0.f, dsum);
+      Oq[kc] = live ? O[at] : 0.f;
     }
-    const float Dc = mha_sum4(dsum);              // sum_dv dO[q][dv] O[q][dv] of the lane's query
+    // D = sum_dv dO[q][dv] O[q][dv] of the lane's query: the diagonal of O dO^T from the same instruction sequence, with the same
+    // operand roles, as V dO^T below -- dS = P (dO V^T - D) is a cancellation, and summed in one order the two sides round alike:
+    // for a query whose weight sits on one key (O = that key's V) the difference is exactly 0, not a rounding residue
+    f32x4 dd = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) dd = mha_mfma(Oq[kc], Gq[kc], dd);  // [row = query 4 g + i][column = query c]
+    const float diag = (c & 3) == 0 ? dd[0] : (c & 3) == 1 ? dd[1] : (c & 3) == 2 ? dd[2] : dd[3];
+    const float Dc = __shfl(diag, 16 * (c >> 2) + c);  // (row c of column c is element c & 3 of the lane g = c >> 2)
     const float Lc = live ? lse_h[q] : 0.f;
     // ... and with (lane / 16, j -> query 4 g + j; lane % 16 -> feature): Q, dO at [q0 + 4 g + j][16 dt + c]
     float Qa[NDT][4], Ga[NDT][4], Dr[4], Lr[4];
