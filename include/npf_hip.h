@@ -22,6 +22,8 @@
  *   npf_mixture_score    log density / PIT / CRPS of an observation under that mixture (inference; no reference counterpart)
  *   npf_waveform_match   overlap / match / mismatch of predicted against reference waveforms over a time-shift grid (inference; no
  *                        reference counterpart)
+ *   npf_waveform_match_ex/_bwd  the same with the unrounded row scalars kept, and the gradient of the match with respect to the
+ *                        predicted amplitude and phase (training on the mismatch; no reference counterpart)
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -632,7 +634,7 @@ typedef struct npf_append_pair {
 int npf_append_points(const npf_append_pair_t *pairs, int32_t n_pairs, int32_t *n_valid, const int32_t *n_new, int32_t n_tasks,
                       int32_t n_rows, int32_t capacity, void *stream);
 
-/* ---- waveform match over a time-shift grid (csrc/waveform_kernels.hip; inference, no reference counterpart) -----------------------
+/* ---- waveform match over a time-shift grid and its gradient (csrc/waveform_kernels.hip; no reference counterpart) -----------------
  * Row r = k * n_tasks + b (latent sample k, task b) of h holds the predicted waveform h_t = A_t e^{i phi_t}: A = h[r][t][0],
  * phi = h[r][t][1], h_ld >= 2 floats per point (2: a [n_rows][pts][2] tensor; 4: the raw decoder output of a dy = 2 head, whose first
  * two entries are the head's loc).  g[n_tasks][pts][2] holds the reference g_t = A'_t e^{i phi'_t} of every task, wgt the weight
@@ -668,6 +670,42 @@ int npf_waveform_match(const float *h, int32_t h_ld, const float *g, const float
                        int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
                        double dtau, int32_t n_tau, float *hh, float *gg, float *overlap, float *match, float *mismatch,
                        int32_t *tau_index, float *phase, float *corr, void *workspace, void *stream);
+/* npf_waveform_match with one more output for a backward pass: saved[n_rows][4] = (hh, gg, Re c_{j*}, Im c_{j*}), j* = tau_index
+ * (n_tau == 0: c_0/), the DOUBLES the finishing launch holds before anything is rounded to fp32; zeros for a degenerate row.  saved
+ * may be NULL (and counts as an output when it is not); npf_waveform_match is this call with saved = NULL, and every other output
+ * has the same bits with saved given or not. */
+int npf_waveform_match_ex(const float *h, int32_t h_ld, const float *g, const float *wgt, int32_t wgt_rows, const float *freq,
+                          int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                          double dtau, int32_t n_tau, float *hh, float *gg, float *overlap, float *match, float *mismatch,
+                          int32_t *tau_index, float *phase, float *corr, void *workspace, double *saved, void *stream);
+/* Gradient of the match with respect to the predicted amplitude and phase, at the maximiser the forward found.  For row r with
+ * j* = tau_index[r], tau* = tau0 + j* dtau, theta_t = phi_t - phi'_t + 2 pi f_t tau* (n_tau == 0: no such term, tau_index and freq are
+ * not read), c = c_{j*} = (saved[r][2], saved[r][3]), psi = arg c, hh = saved[r][0], gg = saved[r][1], N = sqrt(hh gg), M = |c| / N:
+ *   dM/dA_t   = w_t (A'_t cos(theta_t - psi) / N - M A_t / hh)
+ *   dM/dphi_t = -w_t A_t A'_t sin(theta_t - psi) / N
+ * Where the maximiser over the grid is unique this is the derivative of the maximum (Danskin); at a tie it is the derivative at the
+ * smallest index, as the forward reports it: a subgradient.  The mismatch is 1 - M: a caller that differentiates the mismatch hands
+ * in the negated incoming gradient.  d_match[n_rows]: the incoming gradient with respect to the match of every row.
+ * d_h has n_bcast * n_rows rows of pts * dh_ld floats: row q * n_rows + r, q < n_bcast, receives d_match[r] / n_bcast times the gradient
+ * above in entries 0 and 1 of every point and exact zeros in entries 2 .. dh_ld - 1 (dh_ld = 4: d_h is the gradient of the raw decoder
+ * output of a dy = 2 head, whose scale entries get none).  n_bcast > 1 serves a match evaluated on the mean over n_bcast latent samples:
+ * the mean is linear, every sample receives 1 / n_bcast of the row's gradient, and the n_bcast row blocks are bit-identical.
+ * EVERY element of d_h is written, so it needs no memset: a removed point (weight not in (0, inf)), a point at or beyond n_valid[b], and
+ * every point of a degenerate row (hh gg == 0, the zeros npf_waveform_match_ex saves; also c == 0, where the phase has no direction)
+ * get exact zeros in all entries.  These are selected, never multiplied in: nothing at or beyond n_valid[b] is read, A, phi, A', phi',
+ * f of a removed point are not read, and a NaN there (or in d_match of a degenerate row) cannot reach d_h.  There is no gradient with
+ * respect to g, wgt or freq.
+ * Arithmetic as in the forward: fp32 inputs widened exactly, everything in double -- the two terms of dM/dA cancel as M -> 1, which is
+ * why the row scalars arrive unrounded -- one sincos per point, one rounding to fp32 per output.  One launch, one thread per point, no
+ * reduction and no atomics: the same inputs give the same bits.  h, g, wgt, wgt_rows, freq, freq_rows, n_valid, n_rows, n_tasks, pts,
+ * tau0, dtau, n_tau: as given to the forward; tau_index, saved, n_valid, d_match are DEVICE data the host never reads: the call sits
+ * in a captured graph.
+ * Status: NPF_EINVAL (nothing launched) for the sizes npf_waveform_match refuses, a NULL h, g, saved, d_match or d_h, n_tau > 0 with
+ * freq or tau_index NULL, n_bcast < 1 or dh_ld < 2. */
+int npf_waveform_match_bwd(const float *h, int32_t h_ld, const float *g, const float *wgt, int32_t wgt_rows, const float *freq,
+                           int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                           double dtau, int32_t n_tau, const int32_t *tau_index, const double *saved, const float *d_match,
+                           int32_t n_bcast, float *d_h, int32_t dh_ld, void *stream);
 
 int npf_version(void);
 

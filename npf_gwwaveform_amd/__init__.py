@@ -9,7 +9,7 @@ from .architectures import (MLP, DotAttender, KeyWeights, MergeFlatInputs, Multi
 from .chain import set_compute_dtype
 from .datasplit import CntxtTrgtGetter, GetRandomIndcs, GetRangeIndcs, get_all_indcs
 from .evaluate import eval_loglike
-from .losses import CNPFLoss, ELBOLossLNPF, LightTailPareto, NLLLossLNPF, SUMOLossLNPF
+from .losses import CNPFLoss, ELBOLossLNPF, LightTailPareto, MismatchLoss, NLLLossLNPF, SUMOLossLNPF
 from .neuralproc import (CNP, LNP, AttnCNP, AttnLNP, Conditioned, HeadDistribution, LatentNeuralProcessFamily, Match,
                          MultivariateNormalDiag, NeuralProcessFamily, Prediction, Reweighted, Score, bootstrap_weights, kfold_weights)
 
@@ -37,7 +37,7 @@ def decode(model: NeuralProcessFamily, X_trgt_enc, R_trgt):
 __all__ = [
     "MLP", "MergeFlatInputs", "merge_flat_input", "DotAttender", "MultiheadAttender", "TransformerAttender", "SelfAttention", "get_attender",
     "NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP", "NPFModel",
-    "CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "LightTailPareto", "MultivariateNormalDiag", "encode", "aggregate", "decode",
+    "CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LightTailPareto", "MultivariateNormalDiag", "encode", "aggregate", "decode",
     "CntxtTrgtGetter", "GetRandomIndcs", "GetRangeIndcs", "get_all_indcs", "set_compute_dtype", "eval_loglike", "HeadDistribution",
     "Conditioned", "Prediction", "Score", "Match", "Reweighted", "KeyWeights", "bootstrap_weights", "kfold_weights",
 ]

@@ -148,6 +148,10 @@ SIGNATURES = {
     "npf_waveform_match_workspace_bytes": (_i64, [_i32, _i32]),
     "npf_waveform_match": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
                                      _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "npf_waveform_match_ex": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
+                                        _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "npf_waveform_match_bwd": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
+                                         _p, _p, _p, _i32, _p, _i32, _p]),
     "npf_version": (C.c_int, []),
 }
 

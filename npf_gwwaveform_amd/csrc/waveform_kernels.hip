@@ -21,6 +21,8 @@ namespace npf {
 
 constexpr int kWfJC = NPF_WAVEFORM_JC;  // time shifts per workgroup of launch 1
 constexpr int kWfThreads = 128;
+constexpr int kWfBwdThreads = 256;  // points per workgroup pass of the backward launch
+constexpr int kWfBwdMaxGridY = 1024;
 constexpr int kWfMaxTau = 65536;
 constexpr double kWfTwoPi = 6.283185307179586476925286766559;
 
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(64) void waveform_finish_kernel(const double* __res
                                                               float* __restrict__ hh, float* __restrict__ gg, float* __restrict__ overlap,
                                                               float* __restrict__ match, float* __restrict__ mismatch,
                                                               int32_t* __restrict__ tau_index, float* __restrict__ phase,
-                                                              float* __restrict__ corr) {
+                                                              float* __restrict__ corr, double* __restrict__ saved) {
   const int r = blockIdx.x, lane = threadIdx.x;
   const double* row = ws + (size_t)r * (size_t)row_doubles;
   const double vhh = row[0], vgg = row[1], prod = vhh * vgg;
@@ -157,6 +159,75 @@ __global__ __launch_bounds__(64) void waveform_finish_kernel(const double* __res
   if (mismatch) mismatch[r] = (float)(1.0 - m);
   if (tau_index) tau_index[r] = degenerate ? 0 : best_j;
   if (phase) phase[r] = degenerate ? 0.f : (float)atan2(im, re);
+  if (saved) {  // what the backward launch starts from, unrounded
+    double* sv = saved + 4 * (size_t)r;
+    sv[0] = degenerate ? 0.0 : vhh;
+    sv[1] = degenerate ? 0.0 : vgg;
+    sv[2] = degenerate ? 0.0 : re;
+    sv[3] = degenerate ? 0.0 : im;
+  }
+}
+
+// Backward of the match with respect to (A, phi) at the maximiser the forward found: one thread per point, no reduction.  With
+// c = c_{j*} = |c| e^{i psi}, N = sqrt(hh gg), M = |c| / N and theta_t = phi_t - phi'_t + 2 pi f_t tau*:
+//   dM/dA_t = w_t (A'_t cos(theta_t - psi) / N - M A_t / hh),   dM/dphi_t = -w_t A_t A'_t sin(theta_t - psi) / N,
+// where cos(theta - psi) = (cos theta Re c + sin theta Im c) / |c| and sin(theta - psi) = (sin theta Re c - cos theta Im c) / |c|:
+// one sincos per point and no atan2.  Every element of the n_bcast row blocks of d_h is written; a removed or padded point and a
+// degenerate row are SELECTED to zero (nothing of them is read or multiplied in).  LD: dh_ld when it is 2 or 4 and d_h is aligned
+// to a whole point (one 8- / 16-byte store per point), 0 for any other leading dimension.
+template <int LD>
+__global__ __launch_bounds__(kWfBwdThreads) void waveform_match_bwd_kernel(
+    const float* __restrict__ h, int h_ld, const float* __restrict__ g, const float* __restrict__ wgt, int wgt_per_task,
+    const float* __restrict__ freq, int freq_per_task, const int32_t* __restrict__ n_valid, int n_rows, int n_tasks, int pts, double tau0,
+    double dtau, int n_tau, const int32_t* __restrict__ tau_index, const double* __restrict__ saved, const float* __restrict__ d_match,
+    int n_bcast, float* __restrict__ d_h, int dh_ld) {
+  const int r = blockIdx.x, b = r % n_tasks;
+  const int nv = n_valid ? clamp_count(n_valid, b, pts) : pts;
+  const double* sv = saved + 4 * (size_t)r;
+  const double vhh = sv[0], vgg = sv[1], re = sv[2], im = sv[3];
+  const double prod = vhh * vgg, mag = sqrt(re * re + im * im);
+  const bool live_row = prod > 0.0 && mag > 0.0;  // (a degenerate row; c = 0: no direction to move the phase in, M A / hh = 0)
+  const double nrm = sqrt(prod);
+  const double inv_n = live_row ? 1.0 / nrm : 0.0, m_hh = live_row ? (mag / nrm) / vhh : 0.0;
+  const double ur = live_row ? re / mag : 0.0, ui = live_row ? im / mag : 0.0;  // e^{i psi}
+  const double scale = live_row ? (double)d_match[r] / (double)n_bcast : 0.0;
+  const double tau = n_tau > 0 ? tau0 + (double)tau_index[r] * dtau : 0.0;
+  const float* hr = h + (size_t)r * (size_t)pts * (size_t)h_ld;
+  const float* gr = g + (size_t)b * (size_t)pts * 2;
+  const float* wr = wgt ? wgt + (wgt_per_task ? (size_t)b * (size_t)pts : 0) : nullptr;
+  const float* fr = n_tau > 0 ? freq + (freq_per_task ? (size_t)b * (size_t)pts : 0) : nullptr;
+  const size_t block_stride = (size_t)n_rows * (size_t)pts * (size_t)dh_ld;
+
+  for (int64_t t = (int64_t)blockIdx.y * kWfBwdThreads + threadIdx.x; t < pts; t += (int64_t)gridDim.y * kWfBwdThreads) {
+    float dA = 0.f, dphi = 0.f;
+    if (live_row && t < nv) {
+      const float wf = wr ? wr[t] : 1.f;
+      if (wf > 0.f && wf < INFINITY) {  // (else a removed point: nothing else of it is read)
+        const double w = (double)wf;
+        const double A = (double)hr[(size_t)t * h_ld], ph = (double)hr[(size_t)t * h_ld + 1];
+        const double Ag = (double)gr[2 * (size_t)t], phg = (double)gr[2 * (size_t)t + 1];
+        double theta = ph - phg;
+        if (n_tau > 0) theta += (kWfTwoPi * (double)fr[t]) * tau;
+        double sn, cs;
+        sincos(theta, &sn, &cs);
+        const double cd = cs * ur + sn * ui, sd = sn * ur - cs * ui;  // cos / sin of theta - psi
+        dA = (float)(scale * (w * (Ag * cd * inv_n - m_hh * A)));
+        dphi = (float)(scale * (-(w * A * Ag) * sd * inv_n));
+      }
+    }
+    float* o = d_h + ((size_t)r * (size_t)pts + (size_t)t) * (size_t)dh_ld;
+    for (int q = 0; q < n_bcast; ++q, o += block_stride) {
+      if (LD == 2) {
+        *reinterpret_cast<float2*>(o) = make_float2(dA, dphi);
+      } else if (LD == 4) {
+        *reinterpret_cast<float4*>(o) = make_float4(dA, dphi, 0.f, 0.f);
+      } else {
+        o[0] = dA;
+        o[1] = dphi;
+        for (int e = 2; e < dh_ld; ++e) o[e] = 0.f;
+      }
+    }
+  }
 }
 
 }  // namespace npf
@@ -167,17 +238,17 @@ extern "C" int64_t npf_waveform_match_workspace_bytes(int32_t n_rows, int32_t n_
   return (int64_t)n_rows * wf_row_doubles(n_tau) * (int64_t)sizeof(double);
 }
 
-extern "C" int npf_waveform_match(const float* h, int32_t h_ld, const float* g, const float* wgt, int32_t wgt_rows, const float* freq,
-                                  int32_t freq_rows, const int32_t* n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
-                                  double dtau, int32_t n_tau, float* hh, float* gg, float* overlap, float* match, float* mismatch,
-                                  int32_t* tau_index, float* phase, float* corr, void* workspace, void* stream) {
+extern "C" int npf_waveform_match_ex(const float* h, int32_t h_ld, const float* g, const float* wgt, int32_t wgt_rows, const float* freq,
+                                     int32_t freq_rows, const int32_t* n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                                     double dtau, int32_t n_tau, float* hh, float* gg, float* overlap, float* match, float* mismatch,
+                                     int32_t* tau_index, float* phase, float* corr, void* workspace, double* saved, void* stream) {
   using namespace npf;
   if (!h || !g || !workspace || h_ld < 2 || n_tasks <= 0 || n_rows <= 0 || n_rows > (1 << 24) || n_rows % n_tasks != 0 || pts <= 0)
     return NPF_EINVAL;
   if (n_tau < 0 || n_tau > kWfMaxTau || (n_tau > 0 && !freq)) return NPF_EINVAL;
   if (wgt && wgt_rows != 1 && wgt_rows != n_tasks) return NPF_EINVAL;
   if (freq && freq_rows != 1 && freq_rows != n_tasks) return NPF_EINVAL;
-  if (!hh && !gg && !overlap && !match && !mismatch && !tau_index && !phase && !corr) return NPF_EINVAL;
+  if (!hh && !gg && !overlap && !match && !mismatch && !tau_index && !phase && !corr && !saved) return NPF_EINVAL;
   const int64_t row_doubles = wf_row_doubles(n_tau);
   double* ws = (double*)workspace;
   hipLaunchKernelGGL((waveform_corr_kernel<kWfJC, kWfThreads>), dim3(n_rows, wf_chunks(n_tau)), dim3(kWfThreads), 0, (hipStream_t)stream,
@@ -185,7 +256,47 @@ extern "C" int npf_waveform_match(const float* h, int32_t h_ld, const float* g, 
                      row_doubles);
   NPF_CHECK_LAUNCH();
   hipLaunchKernelGGL(waveform_finish_kernel, dim3(n_rows), dim3(64), 0, (hipStream_t)stream, ws, row_doubles, n_tasks, n_tau, hh, gg,
-                     overlap, match, mismatch, tau_index, phase, corr);
+                     overlap, match, mismatch, tau_index, phase, corr, saved);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_waveform_match(const float* h, int32_t h_ld, const float* g, const float* wgt, int32_t wgt_rows, const float* freq,
+                                  int32_t freq_rows, const int32_t* n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                                  double dtau, int32_t n_tau, float* hh, float* gg, float* overlap, float* match, float* mismatch,
+                                  int32_t* tau_index, float* phase, float* corr, void* workspace, void* stream) {
+  return npf_waveform_match_ex(h, h_ld, g, wgt, wgt_rows, freq, freq_rows, n_valid, n_rows, n_tasks, pts, tau0, dtau, n_tau, hh, gg, overlap,
+                               match, mismatch, tau_index, phase, corr, workspace, nullptr, stream);
+}
+
+extern "C" int npf_waveform_match_bwd(const float* h, int32_t h_ld, const float* g, const float* wgt, int32_t wgt_rows, const float* freq,
+                                      int32_t freq_rows, const int32_t* n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                                      double dtau, int32_t n_tau, const int32_t* tau_index, const double* saved, const float* d_match,
+                                      int32_t n_bcast, float* d_h, int32_t dh_ld, void* stream) {
+  using namespace npf;
+  if (!h || !g || !saved || !d_match || !d_h || h_ld < 2 || dh_ld < 2 || n_bcast < 1 || n_tasks <= 0 || n_rows <= 0 ||
+      n_rows > (1 << 24) || n_rows % n_tasks != 0 || pts <= 0)
+    return NPF_EINVAL;
+  if (n_tau < 0 || n_tau > kWfMaxTau || (n_tau > 0 && (!freq || !tau_index))) return NPF_EINVAL;
+  if (wgt && wgt_rows != 1 && wgt_rows != n_tasks) return NPF_EINVAL;
+  if (freq && freq_rows != 1 && freq_rows != n_tasks) return NPF_EINVAL;
+  const int blocks_y = (int)((((int64_t)pts + kWfBwdThreads - 1) / kWfBwdThreads < kWfBwdMaxGridY)
+                                 ? ((int64_t)pts + kWfBwdThreads - 1) / kWfBwdThreads
+                                 : kWfBwdMaxGridY);
+  const dim3 grid(n_rows, blocks_y), block(kWfBwdThreads);
+  const bool whole = (uintptr_t)d_h % ((size_t)dh_ld * sizeof(float)) == 0;  // one store per point needs the point aligned
+#define NPF_WF_BWD(LD)                                                                                                                   \
+  hipLaunchKernelGGL(waveform_match_bwd_kernel<LD>, grid, block, 0, (hipStream_t)stream, h, h_ld, g, wgt, (int)(wgt_rows != 1), freq,    \
+                     (int)(freq_rows != 1), n_valid, n_rows, n_tasks, pts, tau0, dtau, n_tau, tau_index, saved, d_match, n_bcast, d_h,   \
+                     dh_ld)
+  if (dh_ld == 2 && whole) {
+    NPF_WF_BWD(2);
+  } else if (dh_ld == 4 && whole) {
+    NPF_WF_BWD(4);
+  } else {
+    NPF_WF_BWD(0);
+  }
+#undef NPF_WF_BWD
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }

@@ -308,6 +308,27 @@ def check_match_want(want) -> tuple:
     return tuple(want)
 
 
+def check_taus(taus, have_freqs: bool):
+    """``taus`` as ``None`` or the host triple ``(float tau0, float dtau, int n_tau)``: two finite floats and ``1 <= n_tau <=
+    MATCH_MAX_TAU``, which needs the frequencies; anything else is a ValueError."""
+    if taus is None:
+        return None
+    if isinstance(taus, torch.Tensor) or not isinstance(taus, (tuple, list)) or len(taus) != 3:
+        raise ValueError(f"taus must be None or a host triple (tau0, dtau, n_tau), got {taus!r}")
+    if not have_freqs:
+        raise ValueError("taus (a time-shift grid) needs freqs, the physical frequency of every point")
+    t0, dt, n = taus
+    if any(isinstance(v, (torch.Tensor, bool)) or not isinstance(v, (int, float)) for v in (t0, dt)) \
+            or isinstance(n, bool) or not isinstance(n, int):
+        raise ValueError(f"taus = (tau0, dtau, n_tau) takes two host floats and a host int, got {taus!r}")
+    if n < 1 or n > MATCH_MAX_TAU:
+        raise ValueError(f"taus: n_tau must lie in [1, {MATCH_MAX_TAU}], got {n} (no time maximisation: taus=None)")
+    tau0, dtau = float(t0), float(dt)
+    if not (math.isfinite(tau0) and math.isfinite(dtau)):
+        raise ValueError(f"taus: tau0 and dtau must be finite, got {tau0}, {dtau}")
+    return tau0, dtau, n
+
+
 def check_match_args(h_shape, g, weights=None, freqs=None, taus=None):
     """The shapes and host values of a :func:`waveform_match` call -> ``(R, T, h_ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau)``;
     ``ValueError`` for anything that does not fit.  Reads shapes only, so it runs on tensors of any device: ``h_shape`` = [R, T, >= 2],
@@ -333,21 +354,8 @@ def check_match_args(h_shape, g, weights=None, freqs=None, taus=None):
         return 1 if t.dim() == 1 else B
 
     wgt_rows, freq_rows = rows_of(weights, "weights"), rows_of(freqs, "freqs")
-    tau0, dtau, n_tau = 0.0, 0.0, 0
-    if taus is not None:
-        if isinstance(taus, torch.Tensor) or not isinstance(taus, (tuple, list)) or len(taus) != 3:
-            raise ValueError(f"taus must be None or a host triple (tau0, dtau, n_tau), got {taus!r}")
-        if freqs is None:
-            raise ValueError("taus (a time-shift grid) needs freqs, the physical frequency of every point")
-        t0, dt, n = taus
-        if any(isinstance(v, (torch.Tensor, bool)) or not isinstance(v, (int, float)) for v in (t0, dt)) \
-                or isinstance(n, bool) or not isinstance(n, int):
-            raise ValueError(f"taus = (tau0, dtau, n_tau) takes two host floats and a host int, got {taus!r}")
-        if n < 1 or n > MATCH_MAX_TAU:
-            raise ValueError(f"taus: n_tau must lie in [1, {MATCH_MAX_TAU}], got {n} (no time maximisation: taus=None)")
-        tau0, dtau, n_tau = float(t0), float(dt), n
-        if not (math.isfinite(tau0) and math.isfinite(dtau)):
-            raise ValueError(f"taus: tau0 and dtau must be finite, got {tau0}, {dtau}")
+    taus = check_taus(taus, freqs is not None)
+    tau0, dtau, n_tau = taus if taus is not None else (0.0, 0.0, 0)
     return R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau
 
 
@@ -391,17 +399,99 @@ def waveform_match(h: torch.Tensor, g: torch.Tensor, weights: Optional[torch.Ten
     weights = weights.detach().contiguous() if weights is not None else None
     freqs = freqs.detach().contiguous() if freqs is not None and n_tau > 0 else None
     nv = counts_i32(n_valid, B) if n_valid is not None else None
+    return _match_launch(h, g, weights, freqs, nv, (R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau), want, corr, None)
+
+
+def _match_launch(h, g, weights, freqs, nv, geo, want, corr, saved) -> WaveformMatch:
+    """The two forward launches on prepared (detached, contiguous) tensors; ``saved``: ``None`` or the float64 [R, 4] tensor that
+    takes the unrounded row scalars (``npf_waveform_match_ex``)."""
+    R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau = geo
     lib = L.load()
     ws = _match_workspace(h.device, int(lib.npf_waveform_match_workspace_bytes(R, n_tau)))
     new = lambda n, dtype=torch.float32: torch.empty((n,), dtype=dtype, device=h.device)  # noqa: E731
     out = {name: (new(B if name == "gg" else R, torch.int32 if name == "tau_index" else torch.float32) if name in want else None)
            for name in MATCH_NAMES}
     c = torch.empty((R, max(n_tau, 1), 2), dtype=torch.float32, device=h.device) if corr else None
-    L.check(lib.npf_waveform_match(L.ptr(h), ld, L.ptr(g), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows,
-                                   _iptr(nv) if nv is not None else None, R, B, T, tau0, dtau, n_tau,
-                                   *(out[name].data_ptr() if out[name] is not None else None for name in MATCH_NAMES),
-                                   L.ptr(c), ws.data_ptr(), L.stream_ptr()), "npf_waveform_match")
+    args = (L.ptr(h), ld, L.ptr(g), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows, _iptr(nv) if nv is not None else None, R, B, T,
+            tau0, dtau, n_tau, *(out[name].data_ptr() if out[name] is not None else None for name in MATCH_NAMES), L.ptr(c),
+            ws.data_ptr())
+    if saved is None:
+        L.check(lib.npf_waveform_match(*args, L.stream_ptr()), "npf_waveform_match")
+    else:
+        L.check(lib.npf_waveform_match_ex(*args, saved.data_ptr(), L.stream_ptr()), "npf_waveform_match_ex")
     return WaveformMatch(*(out[name] for name in MATCH_NAMES), c)
+
+
+class _WaveformMismatchFn(torch.autograd.Function):
+    """``mismatch`` [R] of the rows of ``h_eval`` against ``g`` (``npf_waveform_match_ex``, which keeps the unrounded row scalars) and
+    its gradient with respect to ``src`` (``npf_waveform_match_bwd``, one launch that writes every element): ``src`` is ``h_eval``
+    itself (``n_bcast`` = 1) or the [n_bcast * R, T, ld] samples whose mean over the ``n_bcast`` row blocks ``h_eval`` holds."""
+
+    @staticmethod
+    def forward(ctx, src, h_eval, g, weights, freqs, nv, geo, n_bcast):
+        R = geo[0]
+        saved = torch.empty((R, 4), dtype=torch.float64, device=h_eval.device)
+        m = _match_launch(h_eval, g, weights, freqs, nv, geo, ("mismatch", "tau_index"), False, saved)
+        ctx.save_for_backward(h_eval, g, weights, freqs, nv, m.tau_index, saved)
+        ctx.cfg = (geo, n_bcast, tuple(src.shape))
+        ctx.mark_non_differentiable(m.tau_index)
+        return m.mismatch, m.tau_index
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_mismatch, _):
+        h_eval, g, weights, freqs, nv, tau_index, saved = ctx.saved_tensors
+        (R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau), n_bcast, src_shape = ctx.cfg
+        d_match = d_mismatch.neg().contiguous()  # (mismatch = 1 - match)
+        d_src = torch.empty(src_shape, dtype=torch.float32, device=h_eval.device)  # (written whole: no memset)
+        L.check(L.load().npf_waveform_match_bwd(L.ptr(h_eval), ld, L.ptr(g), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows,
+                                                _iptr(nv) if nv is not None else None, R, B, T, tau0, dtau, n_tau, _iptr(tau_index),
+                                                saved.data_ptr(), L.ptr(d_match), n_bcast, L.ptr(d_src), src_shape[2],
+                                                L.stream_ptr()), "npf_waveform_match_bwd")
+        return d_src, None, None, None, None, None, None, None
+
+
+def waveform_mismatch(h: torch.Tensor, g: torch.Tensor, weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None,
+                      taus=None, n_valid: Optional[torch.Tensor] = None, n_bcast: int = 1,
+                      mean: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mismatch`` [R] of :func:`waveform_match` (same arguments, same bits), differentiable with respect to ``h``: the training
+    objective that sees a phase error coherent across the band.  The forward is the two launches of ``npf_waveform_match_ex``, which
+    also keeps ``(hh, gg, c_{j*})`` in double, the backward one ``npf_waveform_match_bwd`` launch that writes the whole gradient of
+    ``h`` [.., T, ld]: entries 0 and 1 of a point get ``-dM/dA`` and ``-dM/dphi`` (``include/npf_hip.h`` has the formulae), entries
+    2 .. ld - 1 (the raw scale of a decoder row), removed and padded points and degenerate rows get exact zeros.  The derivative is
+    taken at the grid time the forward found (Danskin); where two grid times tie it is the derivative at the smaller index, a
+    subgradient.  There is no gradient with respect to ``g``, ``weights`` or ``freqs``: one of them with ``requires_grad`` is a
+    ``ValueError``.  No double backward.  ``n_bcast`` > 1: ``h`` [n_bcast * R, T, ld] holds ``n_bcast`` latent samples of every row
+    (row ``q * R + r``) and ``mean`` [R, T, >= 2] their mean (e.g. of :func:`mixture_summary`; required then, and accepted with
+    ``n_bcast`` = 1 as the mean of one sample), on which the mismatch is evaluated;
+    the mean is linear, so every sample receives ``1 / n_bcast`` of the row's gradient.  No host sync; the workspace is the one of
+    :func:`waveform_match`, so inside a captured graph the call needs one earlier call at these sizes."""
+    if isinstance(n_bcast, bool) or not isinstance(n_bcast, int) or n_bcast < 1:
+        raise ValueError(f"n_bcast must be a host int >= 1, got {n_bcast!r}")
+    if n_bcast > 1 and mean is None:
+        raise ValueError("n_bcast > 1 evaluates the mismatch on `mean`, the mean of the n_bcast samples h holds: give it")
+    h_shape = tuple(getattr(h, "shape", ()))
+    if mean is not None:
+        if len(h_shape) != 3 or h_shape[0] % n_bcast != 0 or h_shape[2] < 2:
+            raise ValueError(f"h must have shape [n_bcast * R, T, >= 2] with n_bcast={n_bcast}, got {list(h_shape)}")
+        if not isinstance(mean, torch.Tensor) or mean.dim() != 3 or tuple(mean.shape[:2]) != (h_shape[0] // n_bcast, h_shape[1]):
+            raise ValueError(f"mean must have shape [R={h_shape[0] // n_bcast}, T={h_shape[1]}, >= 2], got "
+                             f"{list(mean.shape) if isinstance(mean, torch.Tensor) else type(mean).__name__}")
+    h_eval = h if mean is None else mean
+    geo = check_match_args(getattr(h_eval, "shape", ()), g, weights, freqs, taus)
+    for t, what in ((g, "g"), (weights, "weights"), (freqs, "freqs")):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"waveform_mismatch has no gradient with respect to {what}: detach it")
+    for t in (h, mean, g, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    n_tau, B = geo[8], geo[3]
+    h = h.contiguous()
+    h_eval = h.detach() if mean is None else mean.detach().contiguous()
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and n_tau > 0 else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    return _WaveformMismatchFn.apply(h, h_eval, g.detach().contiguous(), weights, freqs, nv, geo, n_bcast)[0]
 
 
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------

@@ -21,7 +21,7 @@ from torch.distributions.kl import kl_divergence
 
 from . import functional as FN
 
-__all__ = ["CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "LightTailPareto", "sum_log_prob"]
+__all__ = ["CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LightTailPareto", "sum_log_prob"]
 
 
 def sum_log_prob(prob, sample):
@@ -163,3 +163,54 @@ class SUMOLossLNPF(_TaskLogLikelihood):
         if m > n_z:
             raise ValueError(f"SUMO needs at least {m} latent samples, got {n_z}")
         return FN.mc_objective(log_w, FN.MC_SUMO, self._tail_probabilities(n_z, log_w.device), m)
+
+
+class MismatchLoss(nn.Module):
+    """``base(pred_outputs, Y_trgt) + lam * mismatch``: a likelihood objective with the waveform mismatch of the prediction against
+    the targets added (:meth:`~npf_gwwaveform_amd.neuralproc.HeadDistribution.mismatch`), the last fine-tuning step of a waveform
+    surrogate.  A per-point Gaussian likelihood does not see a phase error that is coherent across the band; the mismatch sees
+    exactly that.  No counterpart in the reference.
+
+    ``base``: one of the likelihood losses of this module (or any module with their ``forward``), with its own ``reduction``;
+    ``None``: the mismatch alone.  The mismatch depends on the predicted amplitude and phase only, so without ``base`` the
+    predictive scale sigma receives NO gradient and is left wherever it is -- which is why ``base`` exists.  ``lam``: the weight of
+    the mismatch (a host float).  ``weights`` (the caller's ``4 df / S_n(f)``; ``None``: ones) and ``freqs`` (Hz): [T] or [B, T]
+    tensors, kept as non-persistent buffers: they follow ``.to(device)`` and stay out of the ``state_dict``.  A caller whose grid
+    changes per batch updates them in place (``loss.freqs.copy_(f)``); a captured training step reads them as static inputs.
+    ``taus = (tau0, dtau, n_tau)``: the time-shift grid (needs ``freqs``), host numbers that are part of a captured step.
+    ``of="samples"``: the mean over the latent samples of every sample's mismatch; ``of="mean"``: the mismatch of the mixture mean.
+    ``reduction`` ("mean" | "sum" | None) reduces the per-task mismatch over the tasks like the other losses.  Padded targets are
+    taken from the distribution's ``n_trgt``.  The model must predict (amplitude, phase): ``y_dim != 2`` is a ``ValueError``."""
+
+    def __init__(self, base=None, lam=1.0, weights=None, freqs=None, taus=None, of="samples", reduction="mean"):
+        super().__init__()
+        if base is not None and not isinstance(base, nn.Module):
+            raise ValueError(f"base must be None or a loss module, got {type(base).__name__}")
+        if isinstance(lam, (bool, torch.Tensor)) or not isinstance(lam, (int, float)) or not np.isfinite(lam):
+            raise ValueError(f"lam must be a finite host float, got {lam!r}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        if reduction not in ("mean", "sum", None):
+            raise ValueError(f"Unknown {reduction}")
+        for t, what in ((weights, "weights"), (freqs, "freqs")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.dtype != torch.float32:
+                raise ValueError(f"{what} must be None or a float32 tensor of shape [T] or [B, T], got "
+                                 f"{(list(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if t.requires_grad:
+                raise ValueError(f"the mismatch has no gradient with respect to {what}: detach it")
+        self.taus = FN.check_taus(taus, freqs is not None)
+        self.base, self.lam, self.of, self.reduction = base, float(lam), of, reduction
+        self.register_buffer("weights", weights, persistent=False)
+        self.register_buffer("freqs", freqs, persistent=False)
+
+    def forward(self, pred_outputs, Y_trgt):
+        p_yCc = pred_outputs[0]
+        if not hasattr(p_yCc, "mismatch"):
+            raise ValueError(f"MismatchLoss needs the predictive distribution of this package's models, got {type(p_yCc).__name__}")
+        mm = p_yCc.mismatch(Y_trgt, weights=self.weights, freqs=self.freqs, taus=self.taus, of=self.of).mean(0)  # [B]
+        if self.reduction is not None:
+            mm = mm.mean(0) if self.reduction == "mean" else mm.sum(0)
+        loss = self.lam * mm
+        return loss if self.base is None else self.base(pred_outputs, Y_trgt) + loss

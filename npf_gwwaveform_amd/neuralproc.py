@@ -167,6 +167,34 @@ class HeadDistribution(Independent):
                      m.tau_index.view(lead) if taus is not None else None, m.phase.view(lead),
                      m.corr.view(*lead, *m.corr.shape[1:]) if corr else None)
 
+    def mismatch(self, Y_ref, weights=None, freqs=None, taus=None, of="samples") -> torch.Tensor:
+        """``mismatch`` of :meth:`match` (same arguments, same bits) as a training objective -> [n_z, B], or [1, B] for
+        ``of="mean"``: differentiable with respect to the raw decoder output, so ``p.mismatch(Y).mean().backward()`` reaches the
+        model's parameters.  The gradient is taken at the grid time the forward found (where two grid times tie: at the earlier one,
+        a subgradient) and flows into the amplitude and phase entries only: the scale entries of the raw output, padded targets
+        (``n_trgt``), removed points and degenerate rows receive exact zeros -- a loss made of the mismatch alone does not train
+        sigma (:class:`~npf_gwwaveform_amd.losses.MismatchLoss` adds a likelihood for that).  ``of="mean"``: the mismatch of the
+        mixture mean; the mean is linear in the samples' locs, so every latent sample receives ``1 / n_z`` of the task's gradient.
+        Forward: the two ``npf_waveform_match_ex`` launches (after one moments-only ``npf_mixture_summary`` for the mean);
+        backward: one ``npf_waveform_match_bwd`` launch.  No host sync: the call and its backward sit in a captured training step
+        (call once at the sizes before capturing: the workspace is allocated then).  The raw decoder output is fp32 in the bf16
+        compute mode as well (the head reads the same tensor), so the objective works there unchanged.  ``match`` stays the
+        inference call: it returns everything else and builds no graph."""
+        if self._y_dim != 2:
+            raise ValueError(f"mismatch needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_match_args((rows, T, ld), Y_ref, weights, freqs, taus)
+        suff = self._suff.reshape(n_z * B, T, 4)
+        if of == "samples":
+            mm = FN.waveform_mismatch(suff, Y_ref, weights, freqs, taus, n_valid=self._n_trgt)
+        else:
+            mean = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt)[0]
+            mm = FN.waveform_mismatch(suff, Y_ref, weights, freqs, taus, n_valid=self._n_trgt, n_bcast=n_z, mean=mean)
+        return mm.view(rows // B, B)
+
 
 class Conditioned:
     """A model conditioned on one context set (:meth:`NeuralProcessFamily.condition`): the encoded context points, their
