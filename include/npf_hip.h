@@ -37,6 +37,8 @@
  *   npf_masked_attn_fwd_loo, npf_loo_mean  the same for every context point over the OTHER points of its task (leave-one-out; inference)
  *   npf_masked_attn_fwd_weighted, npf_weighted_mean  the same for S replicates of one stored context that differ in a weight per key
  *                        (bootstrap multiplicities, fold masks; inference)
+ *   npf_masked_attn_fwd_weighted_ex, npf_masked_attn_bwd_weighted, npf_weighted_mean_bwd  training through such weights at one
+ *                        replicate: the forward pass with its log-sum-exp, and the gradients, the weights' included
  *   npf_append_points    new context rows behind the rows each task of such a padded batch holds (no reference counterpart)
  *   npf_split_heads/npf_merge_heads  MultiheadAttender._make_multiheaded / _concatenate_multiheads
  *                                                         npf/architectures/attention.py:505-527
@@ -614,6 +616,44 @@ int npf_masked_attn_fwd_weighted(const float *q, const float *k, const float *v,
  * Sums and the division are held in double in a fixed order: one rounding, and a second launch gives the same bits. */
 int npf_weighted_mean(const float *R_pt, const float *w, const int32_t *n_valid, int32_t n_tasks, int32_t n_ctx_tasks,
                       int32_t pts_per_task, int32_t F, float *out, void *stream);
+
+/* ---- training through key weights: the log-sum-exp of the weighted forward pass, and the gradients (csrc/masked_kernels.hip,
+ * csrc/layout_kernels.hip) ----------------------------------------------------------------------------------------------------
+ * npf_masked_attn_fwd_weighted_ex: the arguments and the result of npf_masked_attn_fwd_weighted (out is bit-identical) plus
+ * lse (row-major [n_tasks][n_queries], every element written, must not be NULL):
+ *   lse(j, q) = log sum_adm w_k exp(scale <Q_q, K_k>)    (the walk's running maximum + log of its running sum),
+ * 0 for a query without an admissible key or at / beyond n_q_valid. */
+int npf_masked_attn_fwd_weighted_ex(const float *q, const float *k, const float *v, const float *w, const int32_t *n_valid,
+                                    const int32_t *n_q_valid, int32_t n_tasks, int32_t n_ctx_tasks, int32_t n_keys,
+                                    int32_t n_queries, int32_t d, float scale, float *out, float *lse, void *stream);
+/* The backward pass of npf_masked_attn_fwd_weighted_ex at ONE replicate (n_tasks == n_ctx_tasks: task j reads its own q / k / v /
+ * counts and row j of w).  out, lse: what the forward call wrote; d_out: PT32 like out.  With
+ *   a_qk = scale <q_q, k_k> + log w_k,   p_qk = exp(a_qk - lse_q),   D_q = <d_out_q, out_q>,   dA_qk = p_qk (<d_out_q, v_k> - D_q)
+ * over the admissible keys (k < n_valid[j] and 0 < w_k < +inf) and the queries below n_q_valid[j] (NULL: all):
+ *   d_q(q) = scale sum_k dA_qk k_k      d_k(k) = scale sum_q dA_qk q_q      d_v(k) = sum_q p_qk d_out_q
+ *   d_w(k) = (sum_q dA_qk) / w_k        (d a_qk / d w_k = 1 / w_k;  d_w: row-major [n_tasks][n_keys])
+ * d_q, d_k, d_v: PT32 like q, k, v.  Every element of the four outputs is written (whole tiles): the caller needs no memset.
+ * An inadmissible key -- at or beyond the count, or with a weight that is 0, negative, NaN or Inf -- never meets a multiply, whatever
+ * its K / V rows and its weight hold, and gets d_k = d_v = d_w = 0 EXACTLY: a removed point is removed, there is no one-sided
+ * derivative at w = 0.  Queries at / beyond n_q_valid are never read and get d_q = 0; a query without an admissible key contributes
+ * nothing.  At w = 1 everywhere, d_w(k) of a scalar loss is the infinitesimal jackknife: how much the loss changes per unit of
+ * extra weight on point k.  No atomics: the sums over keys and queries have a fixed order, a second launch gives the same bits.
+ * The host never reads w or the counts.  Status: NPF_EINVAL for d % 4 != 0, d > 256, a negative size, a NULL or misaligned pointer. */
+int npf_masked_attn_bwd_weighted(const float *q, const float *k, const float *v, const float *w, const int32_t *n_valid,
+                                 const int32_t *n_q_valid, const float *out, const float *d_out, const float *lse, int32_t n_tasks,
+                                 int32_t n_keys, int32_t n_queries, int32_t d, float scale, float *d_q, float *d_k, float *d_v,
+                                 float *d_w, void *stream);
+/* The backward pass of npf_weighted_mean at ONE replicate (n_tasks == n_ctx_tasks).  out: what the forward call wrote, d_out:
+ * row-major [n_tasks][F] like out.  With W = the sum of the task's admissible weights:
+ *   dR_pt(j, k, :) = (w_k / W) d_out(j, :)          dw(j, k) = <d_out(j, :), R(j, k, :) - out(j, :)> / W
+ * for the admissible points; exact zeros for the others and for a task with W = 0 (no one-sided derivative at w = 0).  dR_pt: PT32
+ * like R_pt, dw: row-major [n_tasks][pts_per_task]; every element of both is written.  W is summed in the forward pass's order;
+ * quotients, products, the scalar product and the division are held in double in a fixed order with one rounding per stored value.
+ * Tiles beyond the count and the rows of inadmissible points are not read.  Status: NPF_EINVAL (nothing launched) for a NULL pointer,
+ * n_tasks < 0, pts_per_task <= 0, F <= 0 or F % 32 != 0, R_pt / out / d_out / dR_pt not 16-byte aligned, w / dw not 4-byte aligned,
+ * or n_tasks * ceil(pts_per_task / 32) above 2^31 - 1 (task and tile are the grid's x index); n_tasks == 0 launches nothing. */
+int npf_weighted_mean_bwd(const float *R_pt, const float *w, const int32_t *n_valid, const float *out, const float *d_out,
+                          int32_t n_tasks, int32_t pts_per_task, int32_t F, float *dR_pt, float *dw, void *stream);
 
 /* ---- growing contexts: rows appended at per-task offsets that are device data (csrc/append_kernels.hip) ----------------------
  * For every pair i < n_pairs (<= NPF_APPEND_MAX_PAIRS), task b and j < clamp(n_new[b], 0, n_rows) (n_new == NULL: j < n_rows):

@@ -4,8 +4,8 @@ MarinerQ/npf_GWwaveform, behind the reference's own module API.  See DESIGN.md.
 The compute runs in hand-written HIP kernels (``csrc/``) reached through a C ABI
 (``include/npf_hip.h``); there is no CPU or eager-PyTorch fallback for the path.
 """
-from .architectures import (MLP, DotAttender, KeyWeights, MergeFlatInputs, MultiheadAttender, SelfAttention, TransformerAttender, get_attender,
-                            merge_flat_input)
+from .architectures import (MLP, DotAttender, KeyWeights, MergeFlatInputs, MultiheadAttender, SelfAttention, TrainKeyWeights,
+                            TransformerAttender, get_attender, merge_flat_input)
 from .chain import set_compute_dtype
 from .datasplit import CntxtTrgtGetter, GetRandomIndcs, GetRangeIndcs, get_all_indcs
 from .evaluate import eval_loglike
@@ -39,5 +39,5 @@ __all__ = [
     "NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP", "NPFModel",
     "CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LightTailPareto", "MultivariateNormalDiag", "encode", "aggregate", "decode",
     "CntxtTrgtGetter", "GetRandomIndcs", "GetRangeIndcs", "get_all_indcs", "set_compute_dtype", "eval_loglike", "HeadDistribution",
-    "Conditioned", "Prediction", "Score", "Match", "Reweighted", "KeyWeights", "bootstrap_weights", "kfold_weights",
+    "Conditioned", "Prediction", "Score", "Match", "Reweighted", "KeyWeights", "TrainKeyWeights", "bootstrap_weights", "kfold_weights",
 ]

@@ -138,6 +138,10 @@ SIGNATURES = {
     "npf_loo_mean": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "npf_masked_attn_fwd_weighted": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_float, _p, _p]),
     "npf_weighted_mean": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "npf_masked_attn_fwd_weighted_ex": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_float, _p, _p, _p]),
+    "npf_masked_attn_bwd_weighted": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_float,
+                                               _p, _p, _p, _p, _p]),
+    "npf_weighted_mean_bwd": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
     "npf_masked_gauss_head_fwd": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p]),
     "npf_masked_gauss_head_bwd": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "npf_mixture_summary": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),

@@ -423,6 +423,15 @@ class LeaveOneOut:
         self.n_valid = n_valid
 
 
+def _has_admissible_key(w, n_valid, n_tasks):
+    """bool [n_tasks]: does row ``j`` of the weights (``n_tasks`` rows of C) hold an admissible key -- below ``n_valid[j]`` and
+    ``0 < w < inf``, the rule of the weighted kernels -- computed on the device, no host read."""
+    w = w.reshape(n_tasks, -1)
+    C = w.shape[1]
+    below = torch.arange(C, device=w.device).view(1, C) < n_valid.clamp(0, C).view(n_tasks, 1)
+    return ((w > 0) & (w < math.inf) & below).any(dim=1)
+
+
 class KeyWeights:
     """The key counts ``n_valid`` [B] of a padded batch with a non-negative weight per (replicate, task, key), ``w`` float [S, B, C]
     (``functional.masked_attention_weighted``): the ``S * B`` tasks handed to ``attend_pt`` are S replicates of the B context tasks in
@@ -437,10 +446,22 @@ class KeyWeights:
 
     def live(self, n_tasks):
         """bool [n_tasks]: does the replicate task have an admissible key (computed on the device, no host read)."""
-        w = self.w.reshape(n_tasks, -1)
-        C = w.shape[1]
-        below = torch.arange(C, device=w.device).view(1, C) < self.n_valid.clamp(0, C).repeat(self.S).view(n_tasks, 1)
-        return ((w > 0) & (w < math.inf) & below).any(dim=1)
+        return _has_admissible_key(self.w, self.n_valid.repeat(self.S), n_tasks)
+
+
+class TrainKeyWeights:
+    """The key counts ``n_valid`` [B] of a padded batch with a weight per (task, key), ``w`` float [B, C], on the TRAINING route
+    (``functional.key_weighted_attention``): one replicate, every task attends over its own keys with ``p_k ~ w[b, k] exp(s_k)``, and
+    the call is differentiable in queries, keys, values and ``w`` (which may require grad).  Handed to ``attend_pt`` in the place of
+    ``n_valid``.  For an attender with learned projections the attender expands the weights per head to [H, B, C] with an op
+    autograd sees, so the heads' gradients add up in ``w.grad`` by themselves."""
+
+    def __init__(self, w, n_valid):
+        self.w, self.n_valid = w, n_valid
+
+    def live(self, n_tasks):
+        """bool [n_tasks]: does the task have an admissible key (computed on the device, no host read, no gradient)."""
+        return _has_admissible_key(self.w.detach(), self.n_valid, n_tasks)
 
 
 def _sample_major(x, S, H, B):
@@ -490,7 +511,8 @@ class DotAttender(nn.Module):
         attention_long.py beyond).  ``n_valid``: device integer tensor [n_tasks], the number of real keys of every task among
         the ``n_keys`` rows (a padded batch): the masked attention kernel (``functional.masked_attention``).  ``n_q_valid`` (with
         ``n_valid`` only): the number of real queries of every task; the rows beyond come back as zeros and are skipped.
-        ``n_valid`` as a :class:`LeaveOneOut`: the same with query row ``t`` kept from key row ``t`` (inference only)."""
+        ``n_valid`` as a :class:`LeaveOneOut`: the same with query row ``t`` kept from key row ``t`` (inference only); as a
+        :class:`TrainKeyWeights`: the same with a weight per key, differentiable in the weights too (``forward(w_cntxt=...)``)."""
         from .attention_long import long_scaledot_attention
 
         if n_q_valid is not None and n_valid is None:
@@ -511,6 +533,11 @@ class DotAttender(nn.Module):
             B0 = kw.n_valid.shape[0]  # (the queries and their counts are shared by the replicates: those of the first one are read)
             return FN.masked_attention_weighted(queries_pt[:B0], keys_pt, values_pt, kw.w, kw.n_valid, kw.S * B0, B0, n_keys, n_queries,
                                                 self.kq_size, scale, n_q_valid=None if n_q_valid is None else n_q_valid[:B0])
+        if isinstance(n_valid, TrainKeyWeights):  # (a weight per key of every task's own context, with gradients: forward(w_cntxt=...))
+            _no_bf16_masked()
+            scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
+            return FN.key_weighted_attention(queries_pt, keys_pt, values_pt, n_valid.w, n_valid.n_valid, queries_pt.shape[0], n_keys,
+                                             n_queries, self.kq_size, scale, n_q_valid=n_q_valid)
         if n_valid is not None:
             _no_bf16_masked()
             scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
@@ -637,6 +664,11 @@ class MultiheadAttender(nn.Module):
             Vh = FN.split_heads(self._project(values_pt, B, C, self.value_transform), B, C, self.value_size, H)
             if isinstance(n_valid, LeaveOneOut):  # (the same route on the leave-one-out launch: the row numbers are those of the task)
                 counts = LeaveOneOut(FN.counts_i32(n_valid.n_valid, B).repeat(H))
+            elif isinstance(n_valid, TrainKeyWeights):
+                # (the same route on the key-weighted training kernels: head task h * B + b reads the weights of task b; the
+                # expansion is an autograd op, so d w sums over the heads)
+                w = FN.key_weights_grad(n_valid.w, B, C).unsqueeze(0).expand(H, B, C).reshape(H * B, C)
+                counts = TrainKeyWeights(w, FN.counts_i32(n_valid.n_valid, B).repeat(H))
             else:
                 counts = FN.counts_i32(n_valid, B).repeat(H)
             Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=counts,

@@ -289,6 +289,61 @@ __global__ void weighted_mean_kernel(const float* __restrict__ R, const float* _
   }
 }
 
+// The backward pass of the weighted mean at one replicate (npf_weighted_mean_bwd; task j reads row j of W): with W_j the sum of the
+// admissible weights,  dR[j][k][f] = (w_k / W_j) d_out[j][f]  and  dW[j][k] = <d_out[j], R[j][k] - out[j]> / W_j  for the admissible
+// points, exact zeros for the others and where W_j = 0 -- a removed point is removed: there is no one-sided derivative at w = 0.
+// One workgroup = one task and one tile of 32 points, 256 threads = 8 feature quads x 32 points.  W_j is summed again as the forward
+// kernel sums it (per lane over the tiles, then the butterfly over the 32 lanes, in double: the forward pass's bits); the quotient
+// w / W, the products of dR, the terms of the scalar product, its per-thread sum over the feature quads, the sum over the 8 threads
+// of a point in LDS (in thread order) and the division are held in double with one rounding to fp32 at each store; the order is fixed.
+// Every element of the task's dR tiles and every dW[j][k < pts] is written; the rows of inadmissible points are not read.
+__global__ void weighted_mean_bwd_kernel(const float* __restrict__ R, const float* __restrict__ W, const int32_t* __restrict__ n_valid,
+                                         const float* __restrict__ out, const float* __restrict__ d_out, int pts, int F,
+                                         float* __restrict__ dR, float* __restrict__ dW) {
+  __shared__ double part[8 * 32];
+  const int tiles = (pts + 31) / 32;
+  const int p = threadIdx.x & 31, fg = threadIdx.x >> 5;
+  const size_t task = blockIdx.x / tiles;
+  const int t = blockIdx.x % tiles;
+  const int n = clamp_count(n_valid, task, pts);
+  const float* wrow = W + task * pts;
+  double ws = 0.0;
+  for (int tt = 0; tt * 32 < n; ++tt)
+    if (tt * 32 + p < n) {
+      const float w = wrow[tt * 32 + p];
+      if (w > 0.f && w < INFINITY) ws += (double)w;  // (NaN fails both comparisons)
+    }
+#pragma unroll
+  for (int off = 16; off >= 1; off >>= 1) ws += __shfl_xor(ws, off);
+  const int pt = t * 32 + p;
+  const float w = pt < n ? wrow[pt] : 0.f;
+  const bool ok = ws > 0.0 && w > 0.f && w < INFINITY;
+  const double cw = ok ? (double)w / ws : 0.0;
+  const size_t base = (task * tiles + t) * (size_t)(F * 32);
+  double dot = 0.0;
+  for (int f4 = fg; f4 < F / 4; f4 += 8) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (ok) {
+      const f32x4 r = *(const f32x4*)(R + base + pt_off(f4, p));
+      const f32x4 gq = *(const f32x4*)(d_out + task * F + 4 * f4), o = *(const f32x4*)(out + task * F + 4 * f4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = (float)(cw * (double)gq[j]);
+        dot += (double)gq[j] * ((double)r[j] - (double)o[j]);
+      }
+    }
+    *(f32x4*)(dR + base + pt_off(f4, p)) = v;
+  }
+  part[fg * 32 + p] = dot;
+  __syncthreads();
+  if (fg == 0 && pt < pts) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += part[k * 32 + p];
+    dW[task * pts + pt] = ok ? (float)(s / ws) : 0.f;
+  }
+}
+
 template <bool MASKED>
 __global__ void mean_bwd_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ n_valid, int n_tasks, int pts, int F,
                                 float* __restrict__ dR, int accumulate) {
@@ -483,6 +538,21 @@ extern "C" int npf_weighted_mean(const float* R_pt, const float* w, const int32_
   if ((size_t)n_tasks * (F / 32) > 0x7fffffffu) return NPF_EINVAL;  // (task and feature block are the grid's x index)
   hipLaunchKernelGGL(npf::weighted_mean_kernel, dim3((unsigned)n_tasks * (F / 32)), dim3(256), 0, (hipStream_t)stream, R_pt, w, n_valid,
                      n_ctx_tasks, pts, F, out);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_weighted_mean_bwd(const float* R_pt, const float* w, const int32_t* n_valid, const float* out, const float* d_out,
+                                     int32_t n_tasks, int32_t pts, int32_t F, float* dR_pt, float* dw, void* stream) {
+  if (!R_pt || !w || !n_valid || !out || !d_out || !dR_pt || !dw || n_tasks < 0) return NPF_EINVAL;
+  if (pts <= 0 || F <= 0 || (F & 31)) return NPF_EINVAL;
+  if ((((uintptr_t)R_pt) | ((uintptr_t)out) | ((uintptr_t)d_out) | ((uintptr_t)dR_pt)) & 15) return NPF_EINVAL;
+  if ((((uintptr_t)w) | ((uintptr_t)dw)) & 3) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  const size_t blocks = (size_t)n_tasks * ((pts + 31) / 32);
+  if (blocks > 0x7fffffffu) return NPF_EINVAL;  // (task and tile are the grid's x index)
+  hipLaunchKernelGGL(npf::weighted_mean_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, R_pt, w, n_valid, out,
+                     d_out, pts, F, dR_pt, dw);
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }

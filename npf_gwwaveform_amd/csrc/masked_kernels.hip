@@ -35,6 +35,10 @@
 // task attend over ONE stored copy of its keys / values, each with its own non-negative weight per key (p_k ~ w_k exp(s_k): bootstrap
 // multiplicities, fold masks, down-weighted points).  With every weight 1.0 and S = 1 the result is bit-identical to
 // npf_masked_attn_fwd_nq on the same tensors.
+//
+// Training through key weights (npf_masked_attn_fwd_weighted_ex: a copy of the weighted forward kernel that also stores the
+// log-sum-exp; npf_masked_attn_bwd_weighted: two backward kernels of their own at one replicate): gradients with respect to
+// queries, keys, values AND the weights, d_w_k = (sum_q dA_qk) / w_k, reduced in the d_k / d_v workgroup -- no atomics.
 #include "npf_common.hpp"
 
 namespace npf {
@@ -460,6 +464,123 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_weighted_kernel(const flo
   }
 }
 
+// The weighted forward kernel with its log-sum-exp (npf_masked_attn_fwd_weighted_ex, the forward pass of the training route): the
+// kernel above line for line -- a kernel of its own rather than a flag of a shared body, so that the instance above keeps its
+// schedule -- which also stores the walk's m + log l = log sum_k w_k exp(scale <q, k>) over the admissible keys per (task, query),
+// 0 for a query without an admissible key or at / beyond the count.  The additions are stores only: O has the bits of the kernel above.
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_fwd_weighted_lse_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                          const float* __restrict__ V, const float* __restrict__ W,
+                                                                          const int32_t* __restrict__ n_valid,
+                                                                          const int32_t* __restrict__ n_q_valid,
+                                                                          float* __restrict__ O, float* __restrict__ lse,
+                                                                          int n_ctx_tasks, int n_keys, int T, int Fp, int d,
+                                                                          float scale) {
+  using G = MkGeom<DP>;
+  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
+  __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
+  __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
+  __shared__ __attribute__((aligned(16))) float Lw[KB];  // log w of the block's keys, -inf where the key is not admissible
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int qblocks = (T + 63) >> 6;
+  const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
+  const int bc = b % n_ctx_tasks;  // the context task whose rows and counts the replicate reads
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int nv = clamp_count(n_valid, bc, n_keys);  // (uniform over the workgroup)
+  const int nq = n_q_valid != nullptr ? clamp_count(n_q_valid, bc, T) : T;
+  const float* __restrict__ wrow = W + (size_t)b * n_keys;
+  const int q = qb * 64 + wave * 16 + c;
+  if (qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zeros, no key staged
+    if (q < tilesT * 32) {
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+        if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (q < T && g == 0) lse[(size_t)b * T + q] = 0.f;
+    return;
+  }
+  const bool live = q < nq;
+  float Qq[NKC];  // the lane's query as an operand: Q[q][4 kc + g]
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc) Qq[kc] = (live && 4 * kc < d) ? Q[mk_pt(bc, tilesT, Fp, q, 4 * kc) + g] : 0.f;
+  f32x4 o[NDT];  // O^T[dv = 16 dt + 4 g + i][q = c], not yet divided by l
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  for (int key0 = 0; key0 < nv; key0 += KB) {
+    __syncthreads();
+    // mk_stage for K and V at once, with the rows of inadmissible keys as zeros (the weight is read below the count only)
+    for (int i = tid; i < KB * (DP / 4); i += 256) {
+      const int p = i % KB, f4 = i / KB, key = key0 + p;
+      f32x4 x = {0.f, 0.f, 0.f, 0.f}, y = {0.f, 0.f, 0.f, 0.f};
+      if (key < nv && 4 * f4 < d) {
+        const float wk = wrow[key];
+        if (wk > 0.f && wk < INFINITY) {
+          x = *(const f32x4*)(K + mk_pt(bc, tilesC, Fp, key, 4 * f4));
+          y = *(const f32x4*)(V + mk_pt(bc, tilesC, Fp, key, 4 * f4));
+        }
+      }
+      *(float2*)(Ks + p * LDK + 4 * f4) = float2{x[0], x[1]};
+      *(float2*)(Ks + p * LDK + 4 * f4 + 2) = float2{x[2], x[3]};
+      *(float2*)(Vs + p * LDV + 4 * f4) = float2{y[0], y[1]};
+      *(float2*)(Vs + p * LDV + 4 * f4 + 2) = float2{y[2], y[3]};
+    }
+    if (tid < KB) {
+      const int key = key0 + tid;
+      const float wk = key < nv ? wrow[key] : 0.f;
+      Lw[tid] = (wk > 0.f && wk < INFINITY) ? logf(wk) : -INFINITY;  // (NaN fails both comparisons)
+    }
+    __syncthreads();
+    f32x4 S[NSB];  // S^T[key = key0 + 16 sb + 4 g + i][q = c]
+    float bm = -INFINITY;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) acc = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], acc);
+      const f32x4 lw = *(const f32x4*)(Lw + 16 * sb + 4 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        acc[i] = lw[i] > -INFINITY ? acc[i] * scale + lw[i] : -INFINITY;  // (beyond the count, and the keys without weight)
+        bm = fmaxf(bm, acc[i]);
+      }
+      S[sb] = acc;
+    }
+    // (the block may hold no admissible key: its maximum, and the running one, can be -inf here)
+    const float m_new = fmaxf(m, mk_max4(bm));
+    const float m_ref = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = expf(m - m_ref);  // (0 while m = -inf; 1 where the block holds nothing for the replicate)
+    float ps = 0.f;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        S[sb][i] = expf(S[sb][i] - m_ref);  // (exp(-inf) = 0 for an inadmissible key)
+        ps += S[sb][i];
+      }
+    l = l * alpha + mk_sum4(ps);
+    m = m_new;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) o[dt] = mk_mfma(Vs[(16 * sb + 4 * g + j) * LDV + 16 * dt + c], S[sb][j], o[dt]);
+  }
+  const bool filled = live && l > 0.f;  // (no admissible key, a query beyond the count, the tile's rows beyond T: zeros)
+  const float inv = filled ? 1.f / l : 0.f;
+  if (q < tilesT * 32) {
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+      if (16 * dt + 4 * g < Fp) *(f32x4*)(O + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = filled ? o[dt] * inv : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (q < T && g == 0) lse[(size_t)b * T + q] = filled ? m + logf(l) : 0.f;
+}
+
+
 // d_q: the forward pass's geometry.  dS^T = scale P^T (dP^T - D), P from the log-sum-exp, D[q] = <dO[q], O[q]>.
 template <int DP, bool NQ>
 __global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __restrict__ Q, const float* __restrict__ K,
@@ -633,6 +754,244 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
   }
 }
 
+// Training through key weights (npf_masked_attn_bwd_weighted): the backward pass of masked_attn_fwd_weighted_lse_kernel at one
+// replicate (task j reads row j of W).  With a_qk = scale <q, k> + log w_k, p_qk = exp(a_qk - lse_q), D_q = <dO_q, O_q> and
+// dA_qk = p_qk (<dO_q, v_k> - D_q):  dq_q = scale sum_k dA_qk k_k,  dk_k = scale sum_q dA_qk q_q,  dv_k = sum_q p_qk dO_q  and
+// dw_k = (sum_q dA_qk) / w_k  (d a_qk / d w_k = 1 / w_k).  Two kernels of their own, shaped like masked_attn_dq_kernel and
+// masked_attn_dkv_kernel, so that those keep their schedules.  Admissibility is the forward kernel's: below the count and
+// 0 < w < +inf; an inadmissible key is staged as zeros in its K and its V row and its probability is set to 0, so whatever its rows or
+// its weight hold (NaN / Inf included) never meets a multiply, and its d_k / d_v rows and its d_w are exact zeros -- a removed point is
+// removed: there is no one-sided derivative at w = 0.  A query without an admissible key has lse = 0 and meets no admissible key.
+// n_q_valid may be null: every one of the T queries is real.
+
+// d_q of the weighted attention: masked_attn_dq_kernel with the staging and the log weights of the weighted forward kernel.
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_dq_weighted_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                     const float* __restrict__ V, const float* __restrict__ W,
+                                                                     const int32_t* __restrict__ n_valid,
+                                                                     const int32_t* __restrict__ n_q_valid, const float* __restrict__ O,
+                                                                     const float* __restrict__ dO, const float* __restrict__ lse,
+                                                                     float* __restrict__ dQ, int n_keys, int T, int Fp, int d,
+                                                                     float scale) {
+  using G = MkGeom<DP>;
+  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDA;
+  __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
+  __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
+  __shared__ __attribute__((aligned(16))) float Lw[KB];  // log w of the block's keys, -inf where the key is not admissible
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int qblocks = (T + 63) >> 6;
+  const int qb = blockIdx.x % qblocks, b = blockIdx.x / qblocks;
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int nv = clamp_count(n_valid, b, n_keys);
+  const int nq = n_q_valid != nullptr ? clamp_count(n_q_valid, b, T) : T;
+  const float* __restrict__ wrow = W + (size_t)b * n_keys;
+  const int q = qb * 64 + wave * 16 + c;
+  if (qb * 64 >= nq) {  // (uniform over the workgroup, ahead of every barrier) all 64 queries are padding: zero d_q rows, nothing staged
+    if (q < tilesT * 32) {
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+        if (16 * dt + 4 * g < Fp) *(f32x4*)(dQ + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    return;
+  }
+  const bool live = q < nq;
+  float Qq[NKC], Gq[NKC];
+  f32x4 dd = {0.f, 0.f, 0.f, 0.f};  // D as the diagonal of O dO^T on the matrix unit, summed as dP^T = V dO^T is (masked_attn_dq_kernel)
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc) {
+    const bool ok = live && 4 * kc < d;
+    const size_t at = mk_pt(b, tilesT, Fp, ok ? q : 0, ok ? 4 * kc : 0) + g;
+    Qq[kc] = ok ? Q[at] : 0.f;
+    Gq[kc] = ok ? dO[at] : 0.f;
+    dd = mk_mfma(ok ? O[at] : 0.f, Gq[kc], dd);  // [row = query 4 g + i][column = query c]
+  }
+  const int e = c & 3;
+  const float Dc = __shfl(e == 0 ? dd[0] : e == 1 ? dd[1] : e == 2 ? dd[2] : dd[3], c + 16 * (c >> 2));
+  const float Lc = live ? lse[(size_t)b * T + q] : 0.f;
+  f32x4 dq[NDT];  // dQ^T[f = 16 dt + 4 g + i][q = c]
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int key0 = 0; key0 < nv; key0 += KB) {
+    __syncthreads();
+    // K and V at once, the rows of inadmissible keys as zeros (the weight is read below the count only)
+    for (int i = tid; i < KB * (DP / 4); i += 256) {
+      const int p = i % KB, f4 = i / KB, key = key0 + p;
+      f32x4 x = {0.f, 0.f, 0.f, 0.f}, y = {0.f, 0.f, 0.f, 0.f};
+      if (key < nv && 4 * f4 < d) {
+        const float wk = wrow[key];
+        if (wk > 0.f && wk < INFINITY) {
+          x = *(const f32x4*)(K + mk_pt(b, tilesC, Fp, key, 4 * f4));
+          y = *(const f32x4*)(V + mk_pt(b, tilesC, Fp, key, 4 * f4));
+        }
+      }
+      *(float2*)(Ks + p * LDK + 4 * f4) = float2{x[0], x[1]};
+      *(float2*)(Ks + p * LDK + 4 * f4 + 2) = float2{x[2], x[3]};
+      *(float2*)(Vs + p * LDV + 4 * f4) = float2{y[0], y[1]};
+      *(float2*)(Vs + p * LDV + 4 * f4 + 2) = float2{y[2], y[3]};
+    }
+    if (tid < KB) {
+      const int key = key0 + tid;
+      const float wk = key < nv ? wrow[key] : 0.f;
+      Lw[tid] = (wk > 0.f && wk < INFINITY) ? logf(wk) : -INFINITY;  // (NaN fails both comparisons)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) {
+      f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) {
+        st = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], st);
+        dpt = mk_mfma(Vs[(16 * sb + c) * LDV + 4 * kc + g], Gq[kc], dpt);
+      }
+      const f32x4 lw = *(const f32x4*)(Lw + 16 * sb + 4 * g);
+      f32x4 dst;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float p = (live && lw[i] > -INFINITY) ? expf(st[i] * scale + lw[i] - Lc) : 0.f;
+        dst[i] = scale * p * (dpt[i] - Dc);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) dq[dt] = mk_mfma(Ks[(16 * sb + 4 * g + j) * LDK + 16 * dt + c], dst[j], dq[dt]);
+    }
+  }
+  if (q < tilesT * 32) {  // (zeros where the task has no admissible key, and in the tile's rows beyond T)
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+      if (16 * dt + 4 * g < Fp) *(f32x4*)(dQ + mk_pt(b, tilesT, Fp, q, 16 * dt + 4 * g)) = dq[dt];
+  }
+}
+
+// d_k / d_v / d_w of the weighted attention: masked_attn_dkv_kernel (one workgroup = one task and 16 keys, its four waves take the
+// 16-query blocks in turn and meet in LDS) which also adds up sum_q dA_qk of its 16 keys: per lane over the queries it walks, over the
+// four lanes that share the key, then over the four waves in LDS in wave order -- a fixed order, no atomics.  Every row of d_k / d_v
+// and every d_w[task][key < n_keys] is written.
+template <int DP>
+__global__ __launch_bounds__(256) void masked_attn_dkvw_weighted_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                       const float* __restrict__ V, const float* __restrict__ W,
+                                                                       const int32_t* __restrict__ n_valid,
+                                                                       const int32_t* __restrict__ n_q_valid,
+                                                                       const float* __restrict__ O, const float* __restrict__ dO,
+                                                                       const float* __restrict__ lse, float* __restrict__ dK,
+                                                                       float* __restrict__ dV, float* __restrict__ dW, int n_keys,
+                                                                       int T, int Fp, int d, float scale) {
+  using G = MkGeom<DP>;
+  constexpr int NKC = G::NKC, NDT = G::NDT, LD = G::LDA;
+  __shared__ __attribute__((aligned(16))) float Ks[16 * LD];
+  __shared__ __attribute__((aligned(16))) float Vs[16 * LD];
+  __shared__ f32x4 red[3 * 64];
+  __shared__ float redw[4 * 16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int tilesC = (n_keys + 31) >> 5, tilesT = (T + 31) >> 5;
+  const int kblocks = 2 * tilesC;  // (whole tiles: every row of d_k / d_v is written)
+  const int kb = blockIdx.x % kblocks, b = blockIdx.x / kblocks;
+  const int nv = clamp_count(n_valid, b, n_keys);
+  const int nq = n_q_valid != nullptr ? clamp_count(n_q_valid, b, T) : T;  // (uniform over the workgroup)
+  const int key0 = 16 * kb;
+  float* __restrict__ dwrow = dW + (size_t)b * n_keys;
+  if (key0 >= nv) {  // (uniform over the workgroup)
+    for (int i = tid; i < 16 * (Fp >> 2); i += 256) {
+      const size_t at = mk_pt(b, tilesC, Fp, key0 + (i & 15), 4 * (i >> 4));
+      *(f32x4*)(dK + at) = f32x4{0.f, 0.f, 0.f, 0.f};
+      *(f32x4*)(dV + at) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (tid < 16 && key0 + tid < n_keys) dwrow[key0 + tid] = 0.f;
+    return;
+  }
+  const float* __restrict__ wrow = W + (size_t)b * n_keys;
+  // K and V of the 16 keys, the rows of inadmissible keys as zeros (the weight is read below the count only)
+  for (int i = tid; i < 16 * (DP / 4); i += 256) {
+    const int p = i & 15, f4 = i >> 4, key = key0 + p;
+    f32x4 x = {0.f, 0.f, 0.f, 0.f}, y = {0.f, 0.f, 0.f, 0.f};
+    if (key < nv && 4 * f4 < d) {
+      const float wk = wrow[key];
+      if (wk > 0.f && wk < INFINITY) {
+        x = *(const f32x4*)(K + mk_pt(b, tilesC, Fp, key, 4 * f4));
+        y = *(const f32x4*)(V + mk_pt(b, tilesC, Fp, key, 4 * f4));
+      }
+    }
+    *(float2*)(Ks + p * LD + 4 * f4) = float2{x[0], x[1]};
+    *(float2*)(Ks + p * LD + 4 * f4 + 2) = float2{x[2], x[3]};
+    *(float2*)(Vs + p * LD + 4 * f4) = float2{y[0], y[1]};
+    *(float2*)(Vs + p * LD + 4 * f4 + 2) = float2{y[2], y[3]};
+  }
+  __syncthreads();
+  f32x4 aK[NDT], aV[NDT];  // dK^T / dV^T [f = 16 dt + 4 g + i][key = key0 + c]
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) aK[dt] = aV[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float wc = key0 + c < nv ? wrow[key0 + c] : 0.f;  // the weight of the lane's key
+  const bool key_ok = wc > 0.f && wc < INFINITY;          // (NaN fails both comparisons)
+  const float lwc = key_ok ? logf(wc) : 0.f;
+  float aW = 0.f;  // sum_q dA[q][key = key0 + c] over the queries 4 g + i of the blocks the wave walks
+  for (int q0 = wave * 16; q0 < nq; q0 += 64) {
+    const int q = q0 + c;
+    const bool live = q < nq;
+    // S[q = q0 + 4 g + i][key = c] and dP alike; D and the log-sum-exp of the lane's query c on the way
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dd = {0.f, 0.f, 0.f, 0.f};  // dO O^T [row = query 4 g + i][column = query c]: D on its diagonal, summed as dP is
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) {
+      const bool ok = live && 4 * kc < d;
+      const size_t at = mk_pt(b, tilesT, Fp, ok ? q : 0, ok ? 4 * kc : 0) + g;
+      const float qv = ok ? Q[at] : 0.f, gv = ok ? dO[at] : 0.f;
+      dd = mk_mfma(gv, ok ? O[at] : 0.f, dd);
+      s = mk_mfma(qv, Ks[c * LD + 4 * kc + g], s);
+      dp = mk_mfma(gv, Vs[c * LD + 4 * kc + g], dp);
+    }
+    const float Lc = live ? lse[(size_t)b * T + q] : 0.f;
+    f32x4 pr, ds;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      // (row 4 g + i of column 4 g + i: element i of the lane of this group whose column is 4 g + i; lane 4 g + i holds query
+      // q0 + 4 g + i as its column)
+      const float Di = __shfl(dd[i], 20 * g + i), Li = __shfl(Lc, 4 * g + i);
+      pr[i] = (key_ok && q0 + 4 * g + i < nq) ? expf(s[i] * scale + lwc - Li) : 0.f;
+      const float da = pr[i] * (dp[i] - Di);
+      aW += da;
+      ds[i] = scale * da;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int qj = q0 + 4 * g + j;
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) {
+        const int f = 16 * dt + c;
+        const bool ok = qj < nq && f < d;
+        const size_t at = mk_pt(b, tilesT, Fp, ok ? qj : 0, ok ? (f & ~3) : 0) + (f & 3);
+        aV[dt] = mk_mfma(ok ? dO[at] : 0.f, pr[j], aV[dt]);  // A[row = f][k = query 4 g + j]
+        aK[dt] = mk_mfma(ok ? Q[at] : 0.f, ds[j], aK[dt]);
+      }
+    }
+  }
+  aW = mk_sum4(aW);  // (every lane of key c holds the wave's sum)
+  if (g == 0) redw[wave * 16 + c] = aW;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      const f32x4 mine = pass == 0 ? aK[dt] : aV[dt];
+      __syncthreads();
+      if (wave > 0) red[(wave - 1) * 64 + lane] = mine;
+      __syncthreads();
+      if (wave == 0 && 16 * dt + 4 * g < Fp) {
+        f32x4 t = mine;
+#pragma unroll
+        for (int w = 0; w < 3; ++w) t += red[w * 64 + lane];
+        if (!key_ok) t = f32x4{0.f, 0.f, 0.f, 0.f};
+        *(f32x4*)((pass == 0 ? dK : dV) + mk_pt(b, tilesC, Fp, key0 + c, 16 * dt + 4 * g)) = t;
+      }
+    }
+  }
+  // (redw was written ahead of the barriers above)
+  if (tid < 16 && key0 + tid < n_keys) {
+    const float t = ((redw[tid] + redw[16 + tid]) + redw[32 + tid]) + redw[48 + tid];
+    dwrow[key0 + tid] = key_ok ? t / wc : 0.f;  // (tid < 16: the lane's key c is key0 + tid)
+  }
+}
+
 }  // namespace npf
 
 static bool mk_misaligned(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
@@ -795,13 +1154,13 @@ extern "C" int npf_masked_attn_fwd_loo(const float* q, const float* k, const flo
   return NPF_OK;
 }
 
-extern "C" int npf_masked_attn_fwd_weighted(const float* q, const float* k, const float* v, const float* w, const int32_t* n_valid,
-                                            const int32_t* n_q_valid, int32_t n_tasks, int32_t n_ctx_tasks, int32_t n_keys,
-                                            int32_t n_queries, int32_t d, float scale, float* out, void* stream) {
+static int masked_attn_fwd_weighted(const float* q, const float* k, const float* v, const float* w, const int32_t* n_valid,
+                                    const int32_t* n_q_valid, int32_t n_tasks, int32_t n_ctx_tasks, int32_t n_keys,
+                                    int32_t n_queries, int32_t d, float scale, float* out, float* lse, void* stream) {
   if (n_ctx_tasks <= 0 || n_tasks < 0 || n_tasks % n_ctx_tasks != 0) return NPF_EINVAL;
   const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
   if (rc != NPF_OK) return rc;
-  if (!out || mk_misaligned(out) || (n_keys > 0 && !w) || (((uintptr_t)w) & 3)) return NPF_EINVAL;
+  if (!out || mk_misaligned(out) || (n_keys > 0 && !w) || (((uintptr_t)w) & 3) || (((uintptr_t)lse) & 3)) return NPF_EINVAL;
   if (n_tasks == 0 || n_queries == 0) return NPF_OK;
   const int Fp = npf::round_up(d, 32);
   const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64)), block(256);
@@ -809,9 +1168,63 @@ extern "C" int npf_masked_attn_fwd_weighted(const float* q, const float* k, cons
 #define MK_WGT(DP)                                                                                                                   \
   hipLaunchKernelGGL((npf::masked_attn_fwd_weighted_kernel<DP>), grid, block, 0, st, q, k, v, w, n_valid, n_q_valid, out, n_ctx_tasks, \
                      n_keys, n_queries, Fp, d, scale)
-  MK_DISPATCH(MK_WGT);
+#define MK_WGT_LSE(DP)                                                                                                             \
+  hipLaunchKernelGGL((npf::masked_attn_fwd_weighted_lse_kernel<DP>), grid, block, 0, st, q, k, v, w, n_valid, n_q_valid, out, lse, \
+                     n_ctx_tasks, n_keys, n_queries, Fp, d, scale)
+  if (lse)
+    MK_DISPATCH(MK_WGT_LSE);
+  else
+    MK_DISPATCH(MK_WGT);
+#undef MK_WGT_LSE
 #undef MK_WGT
   NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
+extern "C" int npf_masked_attn_fwd_weighted(const float* q, const float* k, const float* v, const float* w, const int32_t* n_valid,
+                                            const int32_t* n_q_valid, int32_t n_tasks, int32_t n_ctx_tasks, int32_t n_keys,
+                                            int32_t n_queries, int32_t d, float scale, float* out, void* stream) {
+  return masked_attn_fwd_weighted(q, k, v, w, n_valid, n_q_valid, n_tasks, n_ctx_tasks, n_keys, n_queries, d, scale, out, nullptr, stream);
+}
+
+extern "C" int npf_masked_attn_fwd_weighted_ex(const float* q, const float* k, const float* v, const float* w, const int32_t* n_valid,
+                                               const int32_t* n_q_valid, int32_t n_tasks, int32_t n_ctx_tasks, int32_t n_keys,
+                                               int32_t n_queries, int32_t d, float scale, float* out, float* lse, void* stream) {
+  if (!lse) return NPF_EINVAL;
+  return masked_attn_fwd_weighted(q, k, v, w, n_valid, n_q_valid, n_tasks, n_ctx_tasks, n_keys, n_queries, d, scale, out, lse, stream);
+}
+
+extern "C" int npf_masked_attn_bwd_weighted(const float* q, const float* k, const float* v, const float* w, const int32_t* n_valid,
+                                            const int32_t* n_q_valid, const float* out, const float* d_out, const float* lse,
+                                            int32_t n_tasks, int32_t n_keys, int32_t n_queries, int32_t d, float scale, float* d_q,
+                                            float* d_k, float* d_v, float* d_w, void* stream) {
+  const int rc = masked_attn_check(q, k, v, n_valid, n_tasks, n_keys, n_queries, d);
+  if (rc != NPF_OK) return rc;
+  if (!out || !d_out || !lse || !d_q || (n_keys > 0 && (!w || !d_k || !d_v || !d_w))) return NPF_EINVAL;
+  if (mk_misaligned(out, d_out, d_q) || mk_misaligned(d_k, d_v)) return NPF_EINVAL;
+  if ((((uintptr_t)w) | ((uintptr_t)d_w) | ((uintptr_t)lse)) & 3) return NPF_EINVAL;
+  if (n_tasks == 0) return NPF_OK;
+  const int Fp = npf::round_up(d, 32);
+  const dim3 block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (n_queries > 0) {
+    const dim3 grid((unsigned)n_tasks * ((n_queries + 63) / 64));
+#define MK_DQW(DP)                                                                                                                   \
+  hipLaunchKernelGGL((npf::masked_attn_dq_weighted_kernel<DP>), grid, block, 0, st, q, k, v, w, n_valid, n_q_valid, out, d_out, lse, \
+                     d_q, n_keys, n_queries, Fp, d, scale)
+    MK_DISPATCH(MK_DQW);
+#undef MK_DQW
+    NPF_CHECK_LAUNCH();
+  }
+  if (n_keys > 0) {  // (no queries: the walk over them is empty and the kernel stores the zeros)
+    const dim3 grid((unsigned)n_tasks * (2 * ((n_keys + 31) / 32)));
+#define MK_DKVW(DP)                                                                                                                    \
+  hipLaunchKernelGGL((npf::masked_attn_dkvw_weighted_kernel<DP>), grid, block, 0, st, q, k, v, w, n_valid, n_q_valid, out, d_out, lse, \
+                     d_k, d_v, d_w, n_keys, n_queries, Fp, d, scale)
+    MK_DISPATCH(MK_DKVW);
+#undef MK_DKVW
+    NPF_CHECK_LAUNCH();
+  }
   return NPF_OK;
 }
 

@@ -945,6 +945,146 @@ def weighted_mean(R_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor, n_
     return out
 
 
+# ---- training through key weights (npf_masked_attn_fwd_weighted_ex / _bwd_weighted, npf_weighted_mean_bwd) -------------------
+def key_weights_grad(w: torch.Tensor, n_tasks: int, n_keys: int, what: str = "w") -> torch.Tensor:
+    """:func:`key_weights_f32` for the training route: the same checks, but the tensor stays in the autograd graph (no detach); a
+    contiguous fp32 [n_tasks, n_keys] tensor is used as given, so weights overwritten in place are seen by a replayed graph."""
+    if not isinstance(w, torch.Tensor) or not w.is_floating_point():
+        raise ValueError(f"{what} must be a float device tensor [..., {n_keys}] with {n_tasks} rows, got "
+                         f"{w.dtype if isinstance(w, torch.Tensor) else type(w).__name__}")
+    if w.dim() < 2 or w.shape[-1] != n_keys or w.numel() != n_tasks * n_keys:
+        raise ValueError(f"{what} must hold one weight per (task, key): {n_tasks} rows of {n_keys}, got {list(w.shape)}")
+    if not w.is_cuda:
+        raise ValueError(f"{what} must live on the device (its values are read by the kernels, never by the host)")
+    return w.to(torch.float32).contiguous().view(n_tasks, n_keys)
+
+
+class _KeyWeightedAttnFn(torch.autograd.Function):
+    """:class:`_MaskedAttnFn` with a weight per (task, key): ``p_k ~ w_k exp(s_k)`` (``npf_masked_attn_fwd_weighted`` /
+    ``_fwd_weighted_ex`` at one replicate, ``npf_masked_attn_bwd_weighted``), differentiable in q, k, v and w."""
+
+    @staticmethod
+    def forward(ctx, q_pt, k_pt, v_pt, w, n_valid, n_tasks, n_keys, n_queries, d, scale, n_q_valid=None):
+        from . import chain as CH
+
+        q_pt, k_pt, v_pt, w = q_pt.contiguous(), k_pt.contiguous(), v_pt.contiguous(), w.contiguous()
+        train = any(ctx.needs_input_grad[:4])
+        out = torch.empty(CH.pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
+        lse = torch.empty((n_tasks, n_queries), dtype=torch.float32, device=q_pt.device) if train else None
+        if CH.PROFILE is not None:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        name, keep = ("npf_masked_attn_fwd_weighted", ()) if lse is None else ("npf_masked_attn_fwd_weighted_ex", (L.ptr(lse),))
+        L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
+                                        _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks, n_tasks, n_keys, n_queries, d,
+                                        float(scale), L.ptr(out), *keep, L.stream_ptr()), name)
+        if CH.PROFILE is not None:
+            ev1.record()
+            CH.PROFILE.append(("masked_attn_fwd_weighted_kernel", 4 * n_tasks * n_queries * n_keys * d, ev0, ev1,
+                               4 * pad32(d) * n_tasks * (2 * n_queries + 2 * n_keys), "key-weighted attention (flops at full counts)"))
+        ctx.geom = (n_tasks, n_keys, n_queries, d, float(scale))
+        ctx.has_nq = n_q_valid is not None
+        if train:
+            ctx.save_for_backward(q_pt, k_pt, v_pt, w, n_valid, out, lse, *((n_q_valid,) if ctx.has_nq else ()))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from . import chain as CH
+
+        n_tasks, n_keys, n_queries, d, scale = ctx.geom
+        q_pt, k_pt, v_pt, w, n_valid, out, lse = ctx.saved_tensors[:7]
+        g = g.contiguous()
+        dq, dk, dv, dw = torch.empty_like(q_pt), torch.empty_like(k_pt), torch.empty_like(v_pt), torch.empty_like(w)  # (written whole)
+        if CH.PROFILE is not None:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        L.check(L.load().npf_masked_attn_bwd_weighted(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
+                                                      _iptr(ctx.saved_tensors[7]) if ctx.has_nq else None, L.ptr(out), L.ptr(g),
+                                                      L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk),
+                                                      L.ptr(dv), L.ptr(dw), L.stream_ptr()), "npf_masked_attn_bwd_weighted")
+        if CH.PROFILE is not None:
+            ev1.record()
+            CH.PROFILE.append(("masked_attn_bwd_weighted_kernels", 16 * n_tasks * n_queries * n_keys * d, ev0, ev1,
+                               4 * pad32(d) * n_tasks * (6 * n_queries + 4 * n_keys),
+                               "key-weighted attention backward (flops at full counts)"))
+        return dq, dk, dv, dw, None, None, None, None, None, None, None
+
+
+def key_weighted_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor,
+                           n_tasks: int, n_keys: int, n_queries: int, d: int, scale: float,
+                           n_q_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PT32 [n_tasks, n_queries, d]: :func:`masked_attention` with a weight per (task, key) -- softmax probabilities
+    ``p_k ~ w_k exp(scale <q, k>)`` over the keys below ``n_valid[task]`` with ``0 < w_k < inf`` -- DIFFERENTIABLE in ``q_pt``,
+    ``k_pt``, ``v_pt`` and ``w`` (float [n_tasks, n_keys]): the training route of :func:`masked_attention_weighted` at one replicate.
+    An integer weight is "the point appears w times"; with every weight 1.0 the forward bits are those of :func:`masked_attention`.
+    ``d w_k = (sum_q dA_qk) / w_k`` (``include/npf_hip.h`` has the formulae); a key that is not admissible -- beyond the count, or
+    with a weight that is 0, negative, NaN or Inf -- never meets a multiply and gets exact zeros in ``d k``, ``d v`` and ``d w``:
+    a removed point is removed, there is no one-sided derivative at ``w = 0``.  The log-sum-exp is kept only when a gradient is
+    needed (``npf_masked_attn_fwd_weighted_ex``, else ``npf_masked_attn_fwd_weighted``); the backward pass is one
+    ``npf_masked_attn_bwd_weighted`` call (two launches, no atomics, every output written whole).  Counts, ``n_q_valid`` and weights
+    are read by the kernels only: no host sync, and a captured call sees weights overwritten in place.  No double backward."""
+    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
+        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
+    if n_tasks < 0 or n_keys < 0 or n_queries < 0:
+        raise ValueError(f"negative size: n_tasks={n_tasks}, n_keys={n_keys}, n_queries={n_queries}")
+    for what, t, shape in (("q_pt", q_pt, pt_shape(n_tasks, n_queries, d)), ("k_pt", k_pt, pt_shape(n_tasks, n_keys, d)),
+                           ("v_pt", v_pt, pt_shape(n_tasks, n_keys, d))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
+            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    w = key_weights_grad(w, n_tasks, n_keys)
+    n_valid = counts_i32(n_valid, n_tasks)
+    if n_q_valid is not None:
+        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
+    return _KeyWeightedAttnFn.apply(q_pt, k_pt, v_pt, w, n_valid, n_tasks, n_keys, n_queries, d, scale, n_q_valid)
+
+
+class _KeyWeightedMeanFn(torch.autograd.Function):
+    """The ``w``-weighted mean over the admissible points of every task (``npf_weighted_mean`` at one replicate /
+    ``npf_weighted_mean_bwd``), differentiable in the points and in ``w``."""
+
+    @staticmethod
+    def forward(ctx, R_pt, w, n_valid, n_tasks, pts, F):
+        Fp = pad32(F)
+        R_pt, w = R_pt.contiguous(), w.contiguous()
+        out = torch.empty((n_tasks, Fp), dtype=torch.float32, device=R_pt.device)  # (written whole)
+        L.check(L.load().npf_weighted_mean(L.ptr(R_pt), L.ptr(w), _iptr(n_valid), n_tasks, n_tasks, pts, Fp, L.ptr(out), L.stream_ptr()),
+                "npf_weighted_mean")
+        ctx.geo = (n_tasks, pts, Fp)
+        if any(ctx.needs_input_grad[:2]):
+            ctx.save_for_backward(R_pt, w, n_valid, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        n_tasks, pts, Fp = ctx.geo
+        R_pt, w, n_valid, out = ctx.saved_tensors
+        dR, dw = torch.empty_like(R_pt), torch.empty_like(w)  # (written whole)
+        L.check(L.load().npf_weighted_mean_bwd(L.ptr(R_pt), L.ptr(w), _iptr(n_valid), L.ptr(out), L.ptr(g.contiguous()), n_tasks, pts, Fp,
+                                               L.ptr(dR), L.ptr(dw), L.stream_ptr()), "npf_weighted_mean_bwd")
+        return dR, dw, None, None, None, None
+
+
+def key_weighted_mean(R_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
+    """Row-major [n_tasks, pad32(F)]: row ``j`` is the ``w[j]``-weighted mean over the admissible points (below ``n_valid[j]``,
+    ``0 < w < inf``) of task ``j`` of the PT32 tensor ``R_pt`` [n_tasks, pts, F], zeros where the admissible weights sum to 0 --
+    :func:`weighted_mean` at one replicate (``npf_weighted_mean``, the same bits), DIFFERENTIABLE in ``R_pt`` and in ``w`` (float
+    [n_tasks, pts]): ``d r_k = (w_k / W) d out`` and ``d w_k = <d out, r_k - out> / W`` with ``W`` the sum of the admissible weights
+    (``npf_weighted_mean_bwd``: double arithmetic, one rounding, fixed order); exact zeros for the points that are not admissible
+    and for a task with ``W = 0`` -- no one-sided derivative at ``w = 0``.  With integer weights: the mean over the context with
+    its rows repeated.  Counts and weights are read by the kernels only.  No double backward."""
+    if n_tasks < 0 or pts < 1 or F < 1:
+        raise ValueError(f"key_weighted_mean needs n_tasks >= 0, pts >= 1 and F >= 1, got {n_tasks}, {pts}, {F}")
+    if not isinstance(R_pt, torch.Tensor) or tuple(R_pt.shape) != tuple(pt_shape(n_tasks, pts, F)) or R_pt.dtype != torch.float32:
+        raise ValueError(f"R_pt must be an fp32 PT32 tensor of shape {tuple(pt_shape(n_tasks, pts, F))}, got "
+                         f"{(R_pt.dtype, tuple(R_pt.shape)) if isinstance(R_pt, torch.Tensor) else type(R_pt).__name__}")
+    w = key_weights_grad(w, n_tasks, pts)
+    return _KeyWeightedMeanFn.apply(R_pt, w, counts_i32(n_valid, n_tasks), n_tasks, pts, F)
+
+
 def masked_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
     """Mean over the first ``n_valid[task]`` points of a PT32 tensor -> row-major [n_tasks, pad32(F)] (zeros where a task has none):
     ``torch.mean(R, dim=1)`` (npf/neuralproc/np.py:95, attnnp.py:181) of the batch cut per task; counts as in :func:`masked_attention`."""

@@ -27,7 +27,7 @@ from torch.distributions import Independent, Normal
 
 from . import functional as FN
 from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlatInputs, MultiheadAttender, PrefixTail, SelfAttention,
-                            get_attender, merge_flat_input)
+                            TrainKeyWeights, get_attender, merge_flat_input)
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
@@ -688,8 +688,12 @@ def kfold_weights(folds, k) -> torch.Tensor:
 
 
 def _mean_rows(R_pt, pts, B, r, n_valid=None):
-    """Row-major [B, 1, r]: the mean over the ``pts`` points of every task of a PT32 tensor, or over the first ``n_valid[b]`` of them."""
-    m = FN.mean_agg(R_pt, pts, r) if n_valid is None else FN.masked_mean(R_pt, n_valid, B, pts, r)
+    """Row-major [B, 1, r]: the mean over the ``pts`` points of every task of a PT32 tensor, or over the first ``n_valid[b]`` of them,
+    or (``n_valid`` a :class:`TrainKeyWeights`) their weighted mean."""
+    if isinstance(n_valid, TrainKeyWeights):  # (a weight per point, with gradients: forward(w_cntxt=...))
+        m = FN.key_weighted_mean(R_pt, n_valid.w, n_valid.n_valid, B, pts, r)
+    else:
+        m = FN.mean_agg(R_pt, pts, r) if n_valid is None else FN.masked_mean(R_pt, n_valid, B, pts, r)
     return m[:, :r].reshape(B, 1, r)
 
 
@@ -768,19 +772,68 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         one captured step serves every mix of both counts.  Without ``n_cntxt`` the step keeps its path (padded targets are just
         points to the per-point stages); what ties a task's targets together -- the head and the loss, the homoskedastic pooling,
         the target-side mean of the latent path -- reads the counts.  With ``n_cntxt`` the masked attention also skips the
-        queries beyond the count.  Not implemented with ``n_trgt``: ``is_self_attn=True`` and the bf16 compute mode."""
+        queries beyond the count.  Not implemented with ``n_trgt``: ``is_self_attn=True`` and the bf16 compute mode.
+
+        The conditional models (CNP, AttnCNP) also take ``w_cntxt``, a weight per context point: :meth:`_forward_weighted`."""
+        return self._forward_weighted(X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt=n_cntxt, n_trgt=n_trgt)
+
+    def _forward_weighted(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt=None, n_cntxt=None, n_trgt=None, w_cntxt=None):
+        """``forward`` with one more argument; it IS the ``forward`` of CNP and AttnCNP (the base class keeps the reference's
+        argument list plus the counts).
+
+        ``w_cntxt``: a weight per context point -- a float device tensor [B, C] that may require grad.  Point ``k`` of task ``b``
+        enters what ties the points of a task together with weight ``w_cntxt[b, k]``: the mean of CNP becomes
+        ``sum_k w_k r_k / sum_k w_k`` (``functional.key_weighted_mean``), the attention of AttnCNP ``p_k ~ w_k exp(s_k)``
+        (``functional.key_weighted_attention``; scaled-dot, multihead and transformer attention, the weights shared by the heads).
+        With C > 0 the step takes the padded route; ``n_cntxt=None`` then means that every row lies below the count, and ``n_trgt``
+        combines with it as with ``n_cntxt``.  A point is removed unless ``0 < w < inf`` (a weight that is 0, negative, NaN or Inf
+        removes it, whatever its row holds after the per-point encoders), integer weights give what ``forward`` gives on the context
+        with its rows repeated, and all-ones weights give the bits of the ``n_cntxt`` forward.  Everything is differentiable in the
+        weights too: ``w_cntxt.grad`` of a removed point, or beyond the count, is an exact zero (no one-sided derivative at
+        ``w = 0``); see :meth:`influence`.  The range check does not look at the weights, and nothing reads them on the host: a
+        captured step sees weights overwritten in place.  Not implemented with ``w_cntxt``: ``is_self_attn=True``, the bf16
+        compute mode and the latent models (LNP / AttnLNP: q(z | C, T) would need a rule for the targets' weights)."""
         if n_cntxt is not None:
             n_cntxt = self._check_counts(n_cntxt, X_cntxt, "n_cntxt")
         if n_trgt is not None:
             n_trgt = self._check_counts(n_trgt, X_trgt, "n_trgt")
+        if w_cntxt is not None:
+            w_cntxt = self._check_weights(w_cntxt, X_cntxt)
         self._validate_inputs(X_cntxt, Y_cntxt, X_trgt, Y_trgt)
         B, C, _ = X_cntxt.shape
         T = X_trgt.shape[1]
         if T == 0:
             raise ValueError("no target points")
+        if w_cntxt is not None and C > 0:
+            # (the counts' place on the padded route: the kernels that tie a task's points together read the weights with them)
+            full = n_cntxt if n_cntxt is not None else torch.full((B,), C, dtype=torch.int32, device=X_cntxt.device)
+            n_cntxt = TrainKeyWeights(w_cntxt, full)
         fused_t = self._fused_target_side(C, T)
         Xc_pt, R = self._context_stage(X_cntxt, Y_cntxt, n_cntxt, fused_t)
         return self._target_stage(Xc_pt, R, X_trgt, Y_trgt, B, C, n_cntxt, n_trgt, fused_t)
+
+    def influence(self, X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt=None, n_trgt=None) -> torch.Tensor:
+        """[B, C]: the gradient of every task's summed target log-likelihood ``log p(Y_trgt[b] | context b)`` with respect to the
+        weight of each of its context points at ``w_cntxt = 1`` -- the infinitesimal jackknife: how much each observed point drives
+        the prediction, for every point from one forward and one backward pass (``bootstrap`` / ``kfold`` estimate it by
+        predicting again per replicate).  ``n_cntxt`` / ``n_trgt`` as in ``forward``; zeros at and beyond ``n_cntxt[b]``.  Runs in
+        eval mode (restored afterwards) and through ``torch.autograd.grad`` on the weights alone: no parameter's ``.grad`` is
+        touched.  Refused where ``forward(w_cntxt=...)`` is."""
+        self._refuse_weights()
+        B, C, _ = X_cntxt.shape
+        w = torch.ones((B, C), dtype=torch.float32, device=X_cntxt.device, requires_grad=True)
+        if C == 0:
+            return w.detach()
+        was = self.training
+        self.eval()
+        try:
+            with torch.enable_grad():
+                p_yCc = self(X_cntxt, Y_cntxt, X_trgt, Y_trgt, n_cntxt=n_cntxt, n_trgt=n_trgt, w_cntxt=w)[0]
+                ll = p_yCc.sum_log_prob(Y_trgt)  # [n_z = 1, B]
+                (g,) = torch.autograd.grad(ll.sum(), w)
+        finally:
+            self.train(was)
+        return g
 
     def _context_stage(self, X_cntxt, Y_cntxt, n_cntxt, fused_t):
         """Everything ``forward`` runs before it touches the targets -> (encoded context points ``Xc_pt``, representation ``R``).
@@ -1045,6 +1098,27 @@ class NeuralProcessFamily(nn.Module, abc.ABC):
         if _chain.COMPUTE_DTYPE != "fp32":
             raise NotImplementedError(f"{what} is not implemented in the bf16 compute mode (set_compute_dtype('bf16'))")
 
+    def _refuse_weights(self):
+        """What ``forward(w_cntxt=...)`` does not implement."""
+        self._refuse_unimplemented("w_cntxt")
+        if isinstance(self, LatentNeuralProcessFamily):
+            raise NotImplementedError("w_cntxt is not implemented for the latent models (LNP / AttnLNP): q(z | C, T) would need a rule "
+                                      "for the weights of the targets")
+
+    def _check_weights(self, w, X):
+        """The context weights of the batch ``X`` [B, C, .] as the fp32 device tensor [B, C] the kernels read, still in the autograd
+        graph; refuses what the weighted route does not implement.  The values are not looked at."""
+        self._refuse_weights()
+        B, C = X.shape[0], X.shape[1]
+        if not isinstance(w, torch.Tensor) or not w.is_floating_point():
+            raise ValueError(f"w_cntxt must be a float device tensor of shape [{B}, {C}], got "
+                             f"{w.dtype if isinstance(w, torch.Tensor) else type(w).__name__}")
+        if tuple(w.shape) != (B, C):
+            raise ValueError(f"w_cntxt must have shape [{B}, {C}] (one weight per context point), got {list(w.shape)}")
+        if w.device != X.device:
+            raise ValueError(f"w_cntxt lives on {w.device}, the batch on {X.device}")
+        return w.to(torch.float32).contiguous()
+
     def _check_counts(self, n, X, what):
         """The per-task sizes ``what`` (``n_cntxt`` / ``n_trgt``) of the padded batch ``X`` as a device int32 [B] tensor; refuses what
         the padded path does not implement."""
@@ -1297,6 +1371,8 @@ class CNP(NeuralProcessFamily):
         d["XYEncoder"] = merge_flat_input(sub, is_sum_merge=True)
         return d
 
+    forward = NeuralProcessFamily._forward_weighted  # (forward(..., n_cntxt=None, n_trgt=None, w_cntxt=None))
+
     # reference stage API
     def encode_globally(self, X_cntxt, Y_cntxt):
         B, C, _ = X_cntxt.shape
@@ -1399,6 +1475,7 @@ class AttnCNP(NeuralProcessFamily):
             raise NotImplementedError("the HIP path implements attention = 'scaledot', 'multihead', 'transformer'")
 
     dflt_Modules = CNP.dflt_Modules
+    forward = NeuralProcessFamily._forward_weighted  # (forward(..., n_cntxt=None, n_trgt=None, w_cntxt=None))
 
     def _fused_target_side(self, C, T) -> bool:
         from . import x6
@@ -1443,7 +1520,8 @@ class AttnCNP(NeuralProcessFamily):
         elif isinstance(n_valid, LeaveOneOut):  # (the targets are the context points: a task needs two of them to have a key left)
             R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
             live = n_valid.n_valid > 1
-        elif isinstance(n_valid, KeyWeights):  # (B = S replicates x the stored tasks: a replicate needs one key of positive weight)
+        elif isinstance(n_valid, (KeyWeights, TrainKeyWeights)):
+            # (KeyWeights: B = S replicates x the stored tasks; either way a task needs one key of positive weight)
             R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
             live = n_valid.live(B)
         else:

@@ -49,8 +49,9 @@ def get_exponential_decay_gamma(scheduling_factor, max_epochs):
 
 
 def _counts_of(batch: dict) -> dict:
-    """The per-task context / target sizes of a padded batch as the model's keyword arguments (nothing for a batch without them)."""
-    return {k: batch[k] for k in ("n_cntxt", "n_trgt") if batch.get(k) is not None}
+    """The per-task context / target sizes of a padded batch and the weights of its context points (``w_cntxt``) as the model's
+    keyword arguments (nothing for a batch without them)."""
+    return {k: batch[k] for k in ("n_cntxt", "n_trgt", "w_cntxt") if batch.get(k) is not None}
 
 
 class Trainer:
@@ -69,7 +70,9 @@ class Trainer:
         re-captures; ``n_captures`` counts them).  Batches whose context size changes keep ONE graph when they come padded to a
         fixed number of rows with the per-task sizes as ``batch["n_cntxt"]`` (``GetRandomIndcs(is_per_task=True)``), and likewise
         batches whose target size changes with ``batch["n_trgt"]`` (``CntxtTrgtGetter.batch(X, y, n_points=...)``): the sizes
-        are a static input like the other batch tensors, only their shape is part of the graph's signature.  The range check of the inputs (base.py:241-247) stays in the step as a device reduction; its verdict
+        are a static input like the other batch tensors, only their shape is part of the graph's signature.  A batch may also
+        carry ``batch["w_cntxt"]``, a weight per context point [B, C] (``forward(w_cntxt=...)``): a static input too, read by the
+        kernels only, so the replay sees the new weights.  The range check of the inputs (base.py:241-247) stays in the step as a device reduction; its verdict
         is read at the next sync point: call :meth:`check_inputs` (e.g. once per epoch) to get the reference's ValueError."""
         self.model, self.criterion = model, criterion
         # ``defer_input_check``: eagerly launched steps, too, keep the range check of base.py:241-247 on the device and leave its
