@@ -24,6 +24,8 @@
  *                        reference counterpart)
  *   npf_waveform_match_ex/_bwd  the same with the unrounded row scalars kept, and the gradient of the match with respect to the
  *                        predicted amplitude and phase (training on the mismatch; no reference counterpart)
+ *   npf_waveform_loglike  matched-filter SNR and log likelihood of complex data under the predicted waveforms, phase and arrival
+ *                        time maximised or marginalised, and marginal over the latent samples (inference; no reference counterpart)
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -746,6 +748,47 @@ int npf_waveform_match_bwd(const float *h, int32_t h_ld, const float *g, const f
                            int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
                            double dtau, int32_t n_tau, const int32_t *tau_index, const double *saved, const float *d_match,
                            int32_t n_bcast, float *d_h, int32_t dh_ld, void *stream);
+
+/* ---- matched-filter log likelihood of complex data under the predicted waveforms (csrc/waveform_kernels.hip; no reference counterpart)
+ * h, h_ld, wgt, wgt_rows, freq, freq_rows, n_valid, n_rows, n_tasks, pts, tau0, dtau, n_tau: as in npf_waveform_match; row
+ * r = s * n_tasks + b is latent sample s of task b, n_z = n_rows / n_tasks.  d[n_tasks][pts][2] holds the data of every task as
+ * (Re d_t, Im d_t): Cartesian, so neither an atan2 nor an fp32 phase of the data enters anywhere.  w_t is the caller's 4 df / S_n(f_t).
+ * A point is LIVE if t < n_valid[b] and 0 < w_t < +inf; nothing is read of a point that is not live (NaN included); a NaN in h, d or
+ * freq of a LIVE point is the caller's and propagates into the row's outputs and its task's mixtures.  All sums run
+ * over the live points, in double, from fp32 inputs widened exactly:
+ *   kappa_j  = sum_t w_t A_t e^{i (phi_t + 2 pi f_t tau_j)} conj(d_t)      tau_j = tau0 + j dtau, j < n_tau
+ *   kappa_0/ = the same sum without the time term (n_tau == 0: the only candidate, n = 1 below; freq is not read and may be NULL)
+ *   hh = sum_t w_t A_t^2          dd = sum_t w_t |d_t|^2
+ *   x_j = |kappa_j|               j* = the smallest j that attains max_j x_j
+ *   snr      = x_{j*} / sqrt(hh)                  (the optimal SNR is sqrt(hh))
+ *   phase    = arg kappa_{j*}
+ *   lnl_max  = x_{j*} - hh / 2                    (ln Lambda maximised over the phase and the grid times)
+ *   L_j      = ln I0(x_j) - hh / 2                (phase marginalised, uniform prior)
+ *   lnl_marg = logsumexp_j L_j - ln n,  n = max(n_tau, 1)      (phase and time marginalised, uniform over the grid)
+ *   lnl_mix[b]     = logsumexp_s lnl_marg[s n_tasks + b] - ln n_z      (the latent samples marginalised)
+ *   lnl_max_mix[b] = logsumexp_s lnl_max[s n_tasks + b] - ln n_z
+ * The time term has the sign of npf_waveform_match: h is shifted by e^{+i 2 pi f tau}.  A degenerate row, hh == 0 (no live point or a
+ * zero template), gets snr = 0, phase = 0, tau_index = 0, lnl_max = lnl_marg = 0 (Lambda = 1) and zeros in series; it enters the two
+ * mixtures with 0.  The constant -dd / 2 is added to nothing; dd is returned so that the caller can.
+ * ln I0(x) in double: below NPF_LOGLIKE_I0_SWITCH, log1p of the power series sum_{k >= 1} (x^2 / 4)^k / (k!)^2; from there on
+ * x - ln(2 pi x) / 2 + log1p(S), S the first 16 terms of the series in 1 / (8 x) (truncation 2.7e-16 of I0 at the switch point).  No
+ * overflow for any finite x.  Both log-sum-exps are shifted by their maximum, the one over the latent samples as well: rows whose
+ * likelihoods lie more than 745 apart give neither -inf nor NaN.
+ * Launch 1: geometry, recurrence, reduction order and workspace of npf_waveform_match's first launch (per row [hh, dd, Re kappa_0/,
+ * Im kappa_0/, (Re, Im) kappa_j ...]).  Launch 2: one workgroup per task walks its n_z rows in order.  No atomics: a second call on
+ * the same inputs gives the same bits; the host reads nothing, so the call sits in a captured graph.
+ * Outputs, all DOUBLE but tau_index (each may be NULL, at least one must be given; every requested element is written):
+ * hh / snr / lnl_max / lnl_marg / tau_index / phase [n_rows], dd / lnl_mix / lnl_max_mix [n_tasks],
+ * series[n_rows][max(n_tau, 1)][2] = (L_j, x_j / sqrt(hh)).
+ * workspace: npf_waveform_loglike_workspace_bytes(n_rows, n_tau) bytes of device memory, 8-byte aligned; the function equals
+ * npf_waveform_match_workspace_bytes.  Status: NPF_EINVAL (nothing launched) under the rules of npf_waveform_match, d in g's place. */
+#define NPF_LOGLIKE_I0_SWITCH 24.0
+int64_t npf_waveform_loglike_workspace_bytes(int32_t n_rows, int32_t n_tau);
+int npf_waveform_loglike(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                         int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                         double dtau, int32_t n_tau, double *hh, double *dd, double *snr, double *lnl_max, double *lnl_marg,
+                         int32_t *tau_index, double *phase, double *series, double *lnl_mix, double *lnl_max_mix, void *workspace,
+                         void *stream);
 
 int npf_version(void);
 

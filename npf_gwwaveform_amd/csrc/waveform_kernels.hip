@@ -300,3 +300,240 @@ extern "C" int npf_waveform_match_bwd(const float* h, int32_t h_ld, const float*
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }
+
+// ---- matched-filter log likelihood of complex data under the predicted waveforms (npf_waveform_loglike) ------------------------------
+// The data d_t = (Re, Im) are Cartesian, so no atan2 and no fp32 phase of the data enters: with c_t = w_t A_t conj(d_t),
+//   kappa_j = sum_t c_t e^{i (phi_t + 2 pi f_t tau_j)},   hh = sum_t w_t A_t^2,   dd = sum_t w_t |d_t|^2,
+// kappa_0/ the same sum without the time term.  Launch 1 (waveform_filter_kernel) has the geometry, the recurrence, the reduction
+// order and the workspace layout of waveform_corr_kernel: per row [hh, dd, Re kappa_0/, Im kappa_0/, (Re, Im) kappa_j ...].
+// Launch 2 (waveform_loglike_finish_kernel): one workgroup per task walks the task's latent samples in order; per row the maximum of
+// x_j = |kappa_j| with the smallest index, then sum_j exp(L_j - L_max) with L_j = ln I0(x_j) - hh / 2 (lanes, then waves, in a fixed
+// order), the row's outputs, and after the last row the two log-mean-exps over the latent samples (a running maximum: rows whose
+// likelihoods lie further apart than the range of exp cost nothing).  No atomics; every output is a double.
+namespace npf {
+
+constexpr int kWfLlThreads = 256;  // threads of a finishing workgroup
+constexpr double kWfI0Switch = NPF_LOGLIKE_I0_SWITCH;
+constexpr int kWfI0AsymTerms = 16;   // terms of the 1 / (8 x) series above the switch: truncation 2.7e-16 of I0 at x = 24, less beyond
+constexpr int kWfI0PowerTerms = 48;  // cap of the power series below it (40 terms reach 2^-60 of the sum at x = 24)
+
+// ln I0(x), x >= 0, without overflow.  Below the switch point x_s = 24: log1p of the power series I0 - 1 = sum_{k >= 1} (x^2 / 4)^k /
+// (k!)^2 (positive terms: no cancellation, and log1p keeps the relative accuracy as x -> 0).  From x_s on:
+// x - ln(2 pi x) / 2 + log1p(S) with S = sum_{k = 1 .. 16} prod_{m <= k} (2 m - 1)^2 / (8 x m), summed by Horner's rule.
+__device__ __forceinline__ double wf_log_i0(double x) {
+  if (x < kWfI0Switch) {
+    const double q = 0.25 * x * x;
+    double t = q, s = q;
+#pragma unroll
+    for (int k = 2; k <= kWfI0PowerTerms; ++k) {
+      t *= q * (1.0 / (double)(k * k));  // (unrolled: the reciprocal is a constant, no division in the chain)
+      s += t;
+      if (t <= s * 0x1p-60) break;
+    }
+    return log1p(s);
+  }
+  const double u = 0.125 / x;
+  double acc = 0.0;
+#pragma unroll
+  for (int k = kWfI0AsymTerms; k >= 1; --k) acc = u * ((double)((2 * k - 1) * (2 * k - 1)) / (double)k) * (1.0 + acc);
+  return x - 0.5 * log(kWfTwoPi * x) + log1p(acc);
+}
+
+template <int JC, int THREADS>
+__global__ __launch_bounds__(THREADS) void waveform_filter_kernel(const float* __restrict__ h, int h_ld, const float* __restrict__ d,
+                                                                   const float* __restrict__ wgt, int wgt_per_task,
+                                                                   const float* __restrict__ freq, int freq_per_task,
+                                                                   const int32_t* __restrict__ n_valid, int n_tasks, int pts, double tau0,
+                                                                   double dtau, int n_tau, double* __restrict__ ws, int64_t row_doubles) {
+  __shared__ double red[2 * JC * (THREADS / 64)];
+  const int r = blockIdx.x, chunk = blockIdx.y, b = r % n_tasks;
+  const int nv = n_valid ? clamp_count(n_valid, b, pts) : pts;
+  const float* hr = h + (size_t)r * (size_t)pts * (size_t)h_ld;
+  const float* dr = d + (size_t)b * (size_t)pts * 2;
+  const float* wr = wgt ? wgt + (wgt_per_task ? (size_t)b * (size_t)pts : 0) : nullptr;
+  const float* fr = n_tau > 0 ? freq + (freq_per_task ? (size_t)b * (size_t)pts : 0) : nullptr;  // (n_tau == 0: freq is not read)
+  const double tau_c = tau0 + (double)(chunk * JC) * dtau;  // the chunk's first shift
+  const bool first = chunk == 0;
+
+  double acc[2 * JC];  // (Re, Im) of kappa_j, j = chunk * JC + 0 .. JC - 1
+#pragma unroll
+  for (int i = 0; i < 2 * JC; ++i) acc[i] = 0.0;
+  double base[4] = {0.0, 0.0, 0.0, 0.0};  // hh, dd, Re kappa_0/, Im kappa_0/ (chunk 0 only)
+
+  for (int t = threadIdx.x; t < nv; t += THREADS) {
+    const float wf = wr ? wr[t] : 1.f;
+    if (!(wf > 0.f && wf < INFINITY)) continue;  // a removed point: nothing else of it is read
+    const double w = (double)wf;
+    const double A = (double)hr[(size_t)t * h_ld], ph = (double)hr[(size_t)t * h_ld + 1];
+    const double dre = (double)dr[2 * (size_t)t], dim = (double)dr[2 * (size_t)t + 1];
+    const double wa = w * A, cr = wa * dre, ci = -(wa * dim);  // c = w A conj(d)
+    if (first) {
+      double sn, cs;
+      sincos(ph, &sn, &cs);
+      base[0] += wa * A;
+      base[1] += w * (dre * dre + dim * dim);
+      base[2] += cs * cr - sn * ci;
+      base[3] += cs * ci + sn * cr;
+    }
+    if (n_tau > 0) {
+      const double om = kWfTwoPi * (double)fr[t];
+      double sn, cs, ssn, scs;
+      sincos(ph + om * tau_c, &sn, &cs);
+      sincos(om * dtau, &ssn, &scs);
+      double zr = cs * cr - sn * ci, zi = cs * ci + sn * cr;
+#pragma unroll
+      for (int j = 0; j < JC; ++j) {
+        acc[2 * j] += zr;
+        acc[2 * j + 1] += zi;
+        const double nr = zr * scs - zi * ssn;
+        zi = zr * ssn + zi * scs;
+        zr = nr;
+      }
+    }
+  }
+
+  double* row = ws + (size_t)r * (size_t)row_doubles;
+  if (n_tau > 0) block_sum_store<2 * JC, THREADS>(acc, red, row + 4 + 2 * JC * chunk);
+  if (first) block_sum_store<4, THREADS>(base, red, row);
+}
+
+// One workgroup per task: its n_z = n_rows / n_tasks rows in order, then the two log-mean-exps over them.
+__global__ __launch_bounds__(kWfLlThreads) void waveform_loglike_finish_kernel(
+    const double* __restrict__ ws, int64_t row_doubles, int n_rows, int n_tasks, int n_tau, double* __restrict__ hh,
+    double* __restrict__ dd, double* __restrict__ snr, double* __restrict__ lnl_max, double* __restrict__ lnl_marg,
+    int32_t* __restrict__ tau_index, double* __restrict__ phase, double* __restrict__ series, double* __restrict__ lnl_mix,
+    double* __restrict__ lnl_max_mix) {
+  constexpr int WAVES = kWfLlThreads / 64;
+  __shared__ double red_v[WAVES];
+  __shared__ int red_j[WAVES];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = n_tau > 0 ? n_tau : 1, n_z = n_rows / n_tasks;
+  const double log_n = log((double)n);
+  // running log-sum-exp over the rows (thread 0): maximum so far and the sum of exp(value - maximum)
+  double mix_m = 0.0, mix_s = 0.0, mxm_m = 0.0, mxm_s = 0.0;
+
+  for (int s = 0; s < n_z; ++s) {
+    const int r = s * n_tasks + b;
+    const double* row = ws + (size_t)r * (size_t)row_doubles;
+    const double vhh = row[0];
+    const bool degenerate = vhh == 0.0;  // (no live point, or a zero template: Lambda = 1)
+    const double half_hh = 0.5 * vhh, rt_hh = sqrt(vhh);
+    const double* c = n_tau > 0 ? row + 4 : row + 2;  // (no grid: the one candidate is kappa_0/)
+
+    double best = -1.0;
+    int best_j = 0;
+    for (int j = tid; j < n; j += kWfLlThreads) {
+      const double re = c[2 * j], im = c[2 * j + 1], m2 = re * re + im * im;
+      if (m2 > best) {  // (j ascends: the smallest index of the thread stays)
+        best = m2;
+        best_j = j;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const double ob = __shfl_xor(best, off);
+      const int oj = __shfl_xor(best_j, off);
+      if (ob > best || (ob == best && oj < best_j)) {
+        best = ob;
+        best_j = oj;
+      }
+    }
+    __syncthreads();  // (red_* may still be read for the previous row)
+    if (lane == 0) {
+      red_v[wave] = best;
+      red_j[wave] = best_j;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      const double ob = red_v[w];
+      const int oj = red_j[w];
+      if (w == 0 || ob > best || (ob == best && oj < best_j)) {
+        best = ob;
+        best_j = oj;
+      }
+    }
+    const double x_best = sqrt(best), li0_best = wf_log_i0(x_best);  // (every thread: the same bits)
+
+    double sum = 0.0;
+    for (int j = tid; j < n; j += kWfLlThreads) {
+      const double re = c[2 * j], im = c[2 * j + 1], x = sqrt(re * re + im * im), li0 = wf_log_i0(x);
+      sum += exp(li0 - li0_best);
+      if (series) {
+        double* o = series + ((size_t)r * (size_t)n + (size_t)j) * 2;
+        o[0] = degenerate ? 0.0 : li0 - half_hh;
+        o[1] = degenerate ? 0.0 : x / rt_hh;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+    __syncthreads();  // (the maximum has been read by every thread)
+    if (lane == 0) red_v[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+      double total = 0.0;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) total += red_v[w];
+      const double v_max = degenerate ? 0.0 : x_best - half_hh;
+      const double v_marg = degenerate ? 0.0 : (li0_best - half_hh) + (log(total) - log_n);
+      if (hh) hh[r] = vhh;
+      if (dd && s == 0) dd[b] = row[1];
+      if (snr) snr[r] = degenerate ? 0.0 : x_best / rt_hh;
+      if (lnl_max) lnl_max[r] = v_max;
+      if (lnl_marg) lnl_marg[r] = v_marg;
+      if (tau_index) tau_index[r] = degenerate ? 0 : best_j;
+      if (phase) phase[r] = degenerate ? 0.0 : atan2(c[2 * best_j + 1], c[2 * best_j]);
+      if (s == 0) {
+        mix_m = v_marg, mix_s = 1.0, mxm_m = v_max, mxm_s = 1.0;
+      } else {
+        if (v_marg > mix_m) {
+          mix_s = mix_s * exp(mix_m - v_marg) + 1.0;
+          mix_m = v_marg;
+        } else {
+          mix_s += exp(v_marg - mix_m);
+        }
+        if (v_max > mxm_m) {
+          mxm_s = mxm_s * exp(mxm_m - v_max) + 1.0;
+          mxm_m = v_max;
+        } else {
+          mxm_s += exp(v_max - mxm_m);
+        }
+      }
+    }
+  }
+  if (tid == 0) {
+    const double log_nz = log((double)n_z);
+    if (lnl_mix) lnl_mix[b] = mix_m + (log(mix_s) - log_nz);
+    if (lnl_max_mix) lnl_max_mix[b] = mxm_m + (log(mxm_s) - log_nz);
+  }
+}
+
+}  // namespace npf
+
+extern "C" int64_t npf_waveform_loglike_workspace_bytes(int32_t n_rows, int32_t n_tau) {
+  return npf_waveform_match_workspace_bytes(n_rows, n_tau);  // (the same layout)
+}
+
+extern "C" int npf_waveform_loglike(const float* h, int32_t h_ld, const float* d, const float* wgt, int32_t wgt_rows, const float* freq,
+                                    int32_t freq_rows, const int32_t* n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                                    double dtau, int32_t n_tau, double* hh, double* dd, double* snr, double* lnl_max, double* lnl_marg,
+                                    int32_t* tau_index, double* phase, double* series, double* lnl_mix, double* lnl_max_mix,
+                                    void* workspace, void* stream) {
+  using namespace npf;
+  if (!h || !d || !workspace || h_ld < 2 || n_tasks <= 0 || n_rows <= 0 || n_rows > (1 << 24) || n_rows % n_tasks != 0 || pts <= 0)
+    return NPF_EINVAL;
+  if (n_tau < 0 || n_tau > kWfMaxTau || (n_tau > 0 && !freq)) return NPF_EINVAL;
+  if (wgt && wgt_rows != 1 && wgt_rows != n_tasks) return NPF_EINVAL;
+  if (freq && freq_rows != 1 && freq_rows != n_tasks) return NPF_EINVAL;
+  if (!hh && !dd && !snr && !lnl_max && !lnl_marg && !tau_index && !phase && !series && !lnl_mix && !lnl_max_mix) return NPF_EINVAL;
+  const int64_t row_doubles = wf_row_doubles(n_tau);
+  double* ws = (double*)workspace;
+  hipLaunchKernelGGL((waveform_filter_kernel<kWfJC, kWfThreads>), dim3(n_rows, wf_chunks(n_tau)), dim3(kWfThreads), 0,
+                     (hipStream_t)stream, h, h_ld, d, wgt, (int)(wgt_rows != 1), freq, (int)(freq_rows != 1), n_valid, n_tasks, pts, tau0,
+                     dtau, n_tau, ws, row_doubles);
+  NPF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(waveform_loglike_finish_kernel, dim3(n_tasks), dim3(kWfLlThreads), 0, (hipStream_t)stream, ws, row_doubles, n_rows,
+                     n_tasks, n_tau, hh, dd, snr, lnl_max, lnl_marg, tau_index, phase, series, lnl_mix, lnl_max_mix);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}

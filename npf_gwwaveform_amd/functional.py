@@ -329,17 +329,18 @@ def check_taus(taus, have_freqs: bool):
     return tau0, dtau, n
 
 
-def check_match_args(h_shape, g, weights=None, freqs=None, taus=None):
+def check_match_args(h_shape, g, weights=None, freqs=None, taus=None, what="g (the reference waveforms)"):
     """The shapes and host values of a :func:`waveform_match` call -> ``(R, T, h_ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau)``;
     ``ValueError`` for anything that does not fit.  Reads shapes only, so it runs on tensors of any device: ``h_shape`` = [R, T, >= 2],
     ``g`` [B, T, 2] with ``R % B == 0``, ``weights`` / ``freqs`` ``None``, [T] or [B, T], ``taus`` ``None`` or a host triple
-    ``(tau0, dtau, n_tau)`` of two finite floats and ``1 <= n_tau <= MATCH_MAX_TAU``, which needs ``freqs``."""
+    ``(tau0, dtau, n_tau)`` of two finite floats and ``1 <= n_tau <= MATCH_MAX_TAU``, which needs ``freqs``.  ``what``: how an error
+    names ``g``."""
     h_shape = tuple(h_shape)
     if len(h_shape) != 3 or h_shape[2] < 2 or h_shape[0] < 1 or h_shape[1] < 1:
         raise ValueError(f"h must have shape [R, T, >= 2] (amplitude, phase first), got {list(h_shape)}")
     R, T, ld = h_shape
     if not isinstance(g, torch.Tensor) or g.dim() != 3 or g.shape[0] < 1 or tuple(g.shape[1:]) != (T, 2):
-        raise ValueError(f"g (the reference waveforms) must have shape [B, T={T}, 2], got "
+        raise ValueError(f"{what} must have shape [B, T={T}, 2], got "
                          f"{list(g.shape) if isinstance(g, torch.Tensor) else type(g).__name__}")
     B = g.shape[0]
     if R % B != 0:
@@ -492,6 +493,71 @@ def waveform_mismatch(h: torch.Tensor, g: torch.Tensor, weights: Optional[torch.
     freqs = freqs.detach().contiguous() if freqs is not None and n_tau > 0 else None
     nv = counts_i32(n_valid, B) if n_valid is not None else None
     return _WaveformMismatchFn.apply(h, h_eval, g.detach().contiguous(), weights, freqs, nv, geo, n_bcast)[0]
+
+
+# ---- matched-filter log likelihood of complex data (csrc/waveform_kernels.hip) --------------
+LOGLIKE_NAMES = ("hh", "dd", "snr", "lnl_max", "lnl_marg", "tau_index", "phase", "lnl_mix", "lnl_max_mix")
+LOGLIKE_I0_SWITCH = 24.0  # ln I0(x): power series below, the 1 / (8 x) series from here on (NPF_LOGLIKE_I0_SWITCH)
+_LOGLIKE_PER_TASK = ("dd", "lnl_mix", "lnl_max_mix")
+
+
+class WaveformLogLike(NamedTuple):
+    """What :func:`waveform_loglike` returns (float64 but ``tau_index``); the entries that were not asked for are ``None``."""
+    hh: Optional[torch.Tensor]           # [R] sum_t w A^2: the optimal SNR squared
+    dd: Optional[torch.Tensor]           # [B] sum_t w |d|^2
+    snr: Optional[torch.Tensor]          # [R] max_j |kappa_j| / sqrt(hh)
+    lnl_max: Optional[torch.Tensor]      # [R] phase and time maximised
+    lnl_marg: Optional[torch.Tensor]     # [R] phase and time marginalised
+    tau_index: Optional[torch.Tensor]    # [R] int32
+    phase: Optional[torch.Tensor]        # [R]
+    lnl_mix: Optional[torch.Tensor]      # [B] lnl_marg marginalised over the latent samples
+    lnl_max_mix: Optional[torch.Tensor]  # [B] the same of lnl_max
+    series: Optional[torch.Tensor]       # [R, max(n_tau, 1), 2] = (L_j, x_j / sqrt(hh))
+
+
+def check_loglike_args(h_shape, data, weights=None, freqs=None, taus=None):
+    """The shapes and host values of a :func:`waveform_loglike` call -> what :func:`check_match_args` returns, under its rules:
+    ``data`` [B, T, 2] = (Re, Im) stands where its ``g`` stands.  Reads shapes only."""
+    return check_match_args(h_shape, data, weights, freqs, taus, what="data = (Re, Im)")
+
+
+def waveform_loglike(h: torch.Tensor, data: torch.Tensor, weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None,
+                     taus=None, n_valid: Optional[torch.Tensor] = None, want=LOGLIKE_NAMES, series: bool = False) -> WaveformLogLike:
+    """Matched-filter SNR and log likelihood ratio of the complex data ``data`` [B, T, 2] = (Re d, Im d) under the predicted
+    waveforms ``h`` [R, T, >= 2] (amplitude, phase first; row ``s * B + b`` is latent sample ``s`` of task ``b``): with
+    ``kappa_j = sum_t w A e^{i (phi + 2 pi f tau_j)} conj(d)`` over the grid of ``taus = (tau0, dtau, n_tau)`` and ``hh = sum_t w A^2``,
+    ``snr = max_j |kappa_j| / sqrt(hh)`` with ``tau_index`` the first index that attains it and ``phase = arg kappa`` there,
+    ``lnl_max = max_j |kappa_j| - hh / 2``, ``lnl_marg = logsumexp_j (ln I0(|kappa_j|) - hh / 2) - ln n_tau`` and per task the
+    log-mean-exp of both over the ``R / B`` latent samples (``lnl_mix``, ``lnl_max_mix``); ``include/npf_hip.h`` has the contract and
+    the edge cases.  ``-dd / 2`` is added to nothing.  ``weights``, ``freqs``, ``taus``, ``n_valid``: as in :func:`waveform_match`.
+    ``want``: the names out of ``LOGLIKE_NAMES`` to compute; ``series=True`` adds ``(L_j, x_j / sqrt(hh))`` over the whole grid.
+    Every result is float64.  Two ``npf_waveform_loglike`` launches in double arithmetic, inference only, no host sync,
+    deterministic; the workspace is the one of :func:`waveform_match`."""
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or any(w not in LOGLIKE_NAMES for w in want):
+        raise ValueError(f"want must be a tuple / list of names out of {LOGLIKE_NAMES}, got {want!r}")
+    want = tuple(want)
+    R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau = check_loglike_args(getattr(h, "shape", ()), data, weights, freqs, taus)
+    if not want and not series:
+        raise ValueError(f"want must name at least one of {LOGLIKE_NAMES} (or series=True)")
+    for t in (h, data, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    h, data = h.detach().contiguous(), data.detach().contiguous()
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and n_tau > 0 else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    lib = L.load()
+    ws = _match_workspace(h.device, int(lib.npf_waveform_loglike_workspace_bytes(R, n_tau)))
+    out = {name: (torch.empty((B if name in _LOGLIKE_PER_TASK else R,), dtype=torch.int32 if name == "tau_index" else torch.float64,
+                              device=h.device) if name in want else None) for name in LOGLIKE_NAMES}
+    ser = torch.empty((R, max(n_tau, 1), 2), dtype=torch.float64, device=h.device) if series else None
+    dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    per_row = [dptr(out[name]) for name in ("hh", "dd", "snr", "lnl_max", "lnl_marg", "tau_index", "phase")]
+    L.check(lib.npf_waveform_loglike(L.ptr(h), ld, L.ptr(data), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows,
+                                     _iptr(nv) if nv is not None else None, R, B, T, tau0, dtau, n_tau, *per_row, dptr(ser),
+                                     dptr(out["lnl_mix"]), dptr(out["lnl_max_mix"]), ws.data_ptr(), L.stream_ptr()),
+            "npf_waveform_loglike")
+    return WaveformLogLike(*(out[name] for name in LOGLIKE_NAMES), ser)
 
 
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------

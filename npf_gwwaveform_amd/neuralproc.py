@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlat
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "Reweighted", "bootstrap_weights",
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "LogLike", "Reweighted", "bootstrap_weights",
            "kfold_weights"]
 
 
@@ -69,6 +69,22 @@ class Match(NamedTuple):
     tau_index: Optional[torch.Tensor]  # int32: its index on the grid, the smallest one (``taus`` given)
     phase: torch.Tensor                # arg of the correlation there
     corr: Optional[torch.Tensor]       # [.., B, max(n_tau, 1), 2] normalised correlation over the whole grid (``corr=True``)
+
+
+class LogLike(NamedTuple):
+    """Matched-filter likelihood of complex data under the predicted waveforms (:meth:`HeadDistribution.loglike`), float64 (but
+    ``tau_index``).  Per (latent sample, task): [n_z, B] for ``of="samples"``, [1, B] for ``of="mean"``; per task: [B]."""
+    optimal_snr: torch.Tensor          # sqrt(<h|h>)
+    snr: torch.Tensor                  # max over phase and grid times of <d|h> / sqrt(<h|h>)
+    lnl_max: torch.Tensor              # ln Lambda maximised over the phase and the grid times
+    lnl_marg: torch.Tensor             # ln Lambda marginalised over the phase and the grid times (uniform priors)
+    phase: torch.Tensor                # arg of <d|h> at the maximum
+    tau: Optional[torch.Tensor]        # the grid time of the maximum (``taus`` given)
+    tau_index: Optional[torch.Tensor]  # int32: its index on the grid, the smallest one (``taus`` given)
+    lnl: torch.Tensor                  # [B] lnl_marg marginalised over the latent samples: log-mean-exp
+    lnl_max_mix: torch.Tensor          # [B] the same of lnl_max
+    dd: torch.Tensor                   # [B] <d|d>; ln L = ln Lambda - dd / 2 + const
+    series: Optional[torch.Tensor]     # [.., B, max(n_tau, 1), 2] = (L_j, SNR_j) over the whole grid (``series=True``)
 
 
 class HeadDistribution(Independent):
@@ -166,6 +182,44 @@ class HeadDistribution(Independent):
         return Match(m.overlap.view(lead), m.match.view(lead), m.mismatch.view(lead), tau,
                      m.tau_index.view(lead) if taus is not None else None, m.phase.view(lead),
                      m.corr.view(*lead, *m.corr.shape[1:]) if corr else None)
+
+    def loglike(self, data, weights=None, freqs=None, taus=None, of="samples", series=False) -> LogLike:
+        """The matched-filter log likelihood ratio of the complex detector data ``data`` [B, T, 2] = (Re d, Im d) with the predicted
+        waveform ``h = A e^{i phi}`` as the template -> :class:`LogLike`, for a model whose two outputs are (amplitude, phase).
+        With ``<a|b> = sum_t w a conj(b)``, ``weights`` the caller's ``4 df / S_n(f)`` ([T] or [B, T]; ``None``: ones; a point whose
+        weight is not in (0, inf) is removed) and ``taus = (tau0, dtau, n_tau)`` a grid of arrival times (``freqs`` in Hz carries the
+        shift, with the sign of :meth:`match`): ``snr`` and ``lnl_max = max |<d|h>| - <h|h> / 2`` are maximised over the coalescence
+        phase and the grid, ``lnl_marg = logsumexp_j (ln I0(|<d|h_j>|) - <h|h> / 2) - ln n_tau`` is marginalised over both with
+        uniform priors, and ``lnl`` [B] is the log of the mean of ``exp(lnl_marg)`` over the latent samples: the model's own waveform
+        uncertainty marginalised out of the likelihood (``lnl_max_mix``: the same of ``lnl_max``).  ``-<d|d> / 2`` is added to
+        nothing; ``dd`` returns it.  Everything is float64: values reach 1e4 and differences of order 1 are what gets used.
+        ``of="samples"``: on the raw decoder output, [n_z, B]; ``of="mean"``: the likelihood of the mixture-mean amplitude and
+        phase (one moments-only ``npf_mixture_summary`` launch), [1, B], where ``lnl`` is that one row -- as it is for a
+        deterministic model.  Padded targets (``n_trgt``) are left out.  ``series=True`` adds ``(L_j, SNR_j)`` over the grid.
+        Two ``npf_waveform_loglike`` launches; inference only, no host sync, so a ``query`` and its ``loglike`` can be captured in
+        one graph (call once at the sizes before capturing: the workspace is allocated then).
+        Out of scope: gradients of the likelihood; marginalising the head's per-point sigma (only the latent samples are
+        marginalised); distance / amplitude marginalisation (the amplitude-maximised statistic is ``snr ** 2 / 2``, which the
+        caller forms); non-uniform time priors; sub-grid time interpolation."""
+        if self._y_dim != 2:
+            raise ValueError(f"loglike needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_loglike_args((rows, T, ld), data, weights, freqs, taus)
+        with torch.no_grad():
+            if of == "samples":
+                h = self._suff.detach().reshape(rows, T, ld)
+            else:
+                h = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt)[0]
+            want = tuple(k for k in FN.LOGLIKE_NAMES if k != "tau_index" or taus is not None)
+            m = FN.waveform_loglike(h, data, weights, freqs, taus, n_valid=self._n_trgt, want=want, series=series)
+            lead = (rows // B, B)
+            tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
+            return LogLike(m.hh.sqrt().view(lead), m.snr.view(lead), m.lnl_max.view(lead), m.lnl_marg.view(lead), m.phase.view(lead),
+                           tau, m.tau_index.view(lead) if taus is not None else None, m.lnl_mix, m.lnl_max_mix, m.dd,
+                           m.series.view(*lead, *m.series.shape[1:]) if series else None)
 
     def mismatch(self, Y_ref, weights=None, freqs=None, taus=None, of="samples") -> torch.Tensor:
         """``mismatch`` of :meth:`match` (same arguments, same bits) as a training objective -> [n_z, B], or [1, B] for
