@@ -133,7 +133,7 @@ def plain_attention(Q, K, V, counts, scale, dtype):
 
 
 def emulate_loo_kernel(Q, K, V, counts, q_counts, d, slip=None):
-    """The walk of ``masked_attn_fwd_loo_kernel`` in fp32 torch: key blocks of ``key_block(d)``, running maximum m and sum l per
+    """The walk of ``masked_attn_fwd_kernel`` under the ``MkLoo`` rule in fp32 torch: key blocks of ``key_block(d)``, running maximum m and sum l per
     query, the exponentials against ``m_ref`` (0 while m is -inf), the accumulator rescaled by exp(m_old - m_ref), zeros where
     l = 0.  ``slip`` puts one mistake into the walk (never into a kernel):
       ``own_in_max``     the own score is taken out of the probabilities but still enters the running maximum;
