@@ -651,6 +651,8 @@ int npf_masked_attn_bwd_weighted(const float *q, const float *k, const float *v,
  * for the admissible points; exact zeros for the others and for a task with W = 0 (no one-sided derivative at w = 0).  dR_pt: PT32
  * like R_pt, dw: row-major [n_tasks][pts_per_task]; every element of both is written.  W is summed in the forward pass's order;
  * quotients, products, the scalar product and the division are held in double in a fixed order with one rounding per stored value.
+ * The mean in dw is summed again in double and subtracted unrounded (out, rounded to fp32, would cost dw its digits where the
+ * points of a task differ by less than 2^-24 of their size); out must still be a valid pointer and is not read.
  * Tiles beyond the count and the rows of inadmissible points are not read.  Status: NPF_EINVAL (nothing launched) for a NULL pointer,
  * n_tasks < 0, pts_per_task <= 0, F <= 0 or F % 32 != 0, R_pt / out / d_out / dR_pt not 16-byte aligned, w / dw not 4-byte aligned,
  * or n_tasks * ceil(pts_per_task / 32) above 2^31 - 1 (task and tile are the grid's x index); n_tasks == 0 launches nothing. */

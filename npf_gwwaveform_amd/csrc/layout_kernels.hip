@@ -296,9 +296,13 @@ __global__ void weighted_mean_kernel(const float* __restrict__ R, const float* _
 // kernel sums it (per lane over the tiles, then the butterfly over the 32 lanes, in double: the forward pass's bits); the quotient
 // w / W, the products of dR, the terms of the scalar product, its per-thread sum over the feature quads, the sum over the 8 threads
 // of a point in LDS (in thread order) and the division are held in double with one rounding to fp32 at each store; the order is fixed.
+// The mean that dW subtracts is NOT the forward pass's `out`: rounded to fp32 it is off by up to 2^-24 of its size, which is all of
+// r - out where the points of a task differ by less than that (values of 1e3 +- 1e-3).  Every workgroup of a task sums the mean of
+// each feature quad again, in double and in the forward kernel's order (per lane over the tiles, the butterfly over the 32 lanes),
+// and subtracts it unrounded; `out` is kept in the interface and not read.
 // Every element of the task's dR tiles and every dW[j][k < pts] is written; the rows of inadmissible points are not read.
 __global__ void weighted_mean_bwd_kernel(const float* __restrict__ R, const float* __restrict__ W, const int32_t* __restrict__ n_valid,
-                                         const float* __restrict__ out, const float* __restrict__ d_out, int pts, int F,
+                                         const float* __restrict__ /*out*/, const float* __restrict__ d_out, int pts, int F,
                                          float* __restrict__ dR, float* __restrict__ dW) {
   __shared__ double part[8 * 32];
   const int tiles = (pts + 31) / 32;
@@ -320,16 +324,36 @@ __global__ void weighted_mean_bwd_kernel(const float* __restrict__ R, const floa
   const bool ok = ws > 0.0 && w > 0.f && w < INFINITY;
   const double cw = ok ? (double)w / ws : 0.0;
   const size_t base = (task * tiles + t) * (size_t)(F * 32);
+  const bool any = ws > 0.0 && t * 32 < n;  // (uniform over the workgroup: the tile holds a point below the count)
   double dot = 0.0;
-  for (int f4 = fg; f4 < F / 4; f4 += 8) {
+  for (int f4 = fg; f4 < F / 4; f4 += 8) {  // (F / 4 is a multiple of 8: the same trips for every thread)
+    double o[4] = {0.0, 0.0, 0.0, 0.0};  // the task's mean of the feature quad
+    if (any) {
+      for (int tt = 0; tt * 32 < n; ++tt)
+        if (tt * 32 + p < n) {
+          const float wk = wrow[tt * 32 + p];
+          if (wk > 0.f && wk < INFINITY) {
+            const f32x4 r = *(const f32x4*)(R + (task * tiles + tt) * (size_t)(F * 32) + pt_off(f4, p));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] += (double)wk * (double)r[j];
+          }
+        }
+#pragma unroll
+      for (int off = 16; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] += __shfl_xor(o[j], off);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] /= ws;
+    }
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (ok) {
       const f32x4 r = *(const f32x4*)(R + base + pt_off(f4, p));
-      const f32x4 gq = *(const f32x4*)(d_out + task * F + 4 * f4), o = *(const f32x4*)(out + task * F + 4 * f4);
+      const f32x4 gq = *(const f32x4*)(d_out + task * F + 4 * f4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         v[j] = (float)(cw * (double)gq[j]);
-        dot += (double)gq[j] * ((double)r[j] - (double)o[j]);
+        dot += (double)gq[j] * ((double)r[j] - o[j]);
       }
     }
     *(f32x4*)(dR + base + pt_off(f4, p)) = v;

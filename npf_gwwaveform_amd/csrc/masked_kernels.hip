@@ -49,10 +49,10 @@
 //    own0 .. own0 + 15, and the key sub-blocks are 16 rows at multiples of 16, so the own rows of a wave are exactly one sub-block:
 //    its P V product runs on the vector unit, key by key, with the value row replaced by zeros in the lanes of the query it belongs
 //    to (mk_pv_own_rows).  Every other sub-block is the MFMA product.
-//  * LOO: the score contraction is added in segments of 64 features, each a chain of its own from 0, the segments added afterwards:
-//    an fp32 chain rounds at the size of its running sum, and scores that share a large component (|q . k| of 1600 at 256 features)
-//    are told apart only by what those roundings leave.  So at the 128- and 256-wide instances the scores, and the rows that have no
-//    own key (q >= the key count), are NOT bit for bit those of MkPlain; up to 64 features (one segment) they are.
+//  * (every rule, MK_SEG below: the score contraction is added in segments of 64 features, each a chain of its own from 0, the
+//    segments added afterwards: an fp32 chain rounds at the size of its running sum, and scores that share a large component
+//    (|q . k| of 1600 at 256 features) are told apart only by what those roundings leave.  The forward and both backward kernels
+//    segment alike, under every rule, so the rows of a LOO call that have no own key are those of MkPlain.)
 //  * weighted: the weight is per key and task, not per query, so an inadmissible key is staged as zeros in its K AND its V row
 //    (mk_stage_weighted) and its score set to -inf: whatever those rows or the weight hold (NaN / Inf included) never meets a
 //    multiply -- no vector-unit side path.  The score is scale <q, k> + log w, exp(s + log w - m) rather than w exp(s - m): the
@@ -176,6 +176,12 @@ __device__ __forceinline__ void mk_pv_own_rows(const float* Vsb, const f32x4 P, 
   }
 }
 
+// MFMA steps (of 4 features) per segment of the score contraction <q, k>: one chain up to 64 features, chains of 64 features added
+// in order beyond (the 128- and 256-wide instances).  One chain of 64 steps left a score of 100 at 256 features with an error of
+// 2e-5 (its running sum reaches 16 |s|, and each step rounds at that size), and the output with 3e-5 of its size.
+template <int NKC>
+inline constexpr int MK_SEG = NKC > 16 ? 16 : NKC;
+
 template <int DP>
 struct MkGeom {
   static constexpr int KB = DP == 256 ? 16 : 32;  // keys per block: 33 KB of LDS for keys + values at every width
@@ -232,7 +238,7 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
                                                              const R r) {
   using G = MkGeom<DP>;
   constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDB;
-  constexpr int SEG = R::LOO && NKC > 16 ? 16 : NKC;  // MFMA steps (of 4 features) per segment of the score contraction
+  constexpr int SEG = MK_SEG<NKC>;
   __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
   __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
   [[maybe_unused]] float* Lw = nullptr;  // log w of the block's keys
@@ -289,7 +295,7 @@ __global__ __launch_bounds__(256) void masked_attn_fwd_kernel(const float* __res
       float bm = -INFINITY;
 #pragma unroll
       for (int sb = 0; sb < NSB; ++sb) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};  // (one segment, SEG = NKC: the plain chain)
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};  // (one segment, SEG = NKC: one chain)
 #pragma unroll
         for (int k0 = 0; k0 < NKC; k0 += SEG) {
           f32x4 part = {0.f, 0.f, 0.f, 0.f};
@@ -359,7 +365,7 @@ __global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __rest
                                                             const float* __restrict__ dO, const float* __restrict__ lse,
                                                             float* __restrict__ dQ, int n_keys, int T, int Fp, int d, float scale) {
   using G = MkGeom<DP>;
-  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDA;
+  constexpr int KB = G::KB, NSB = G::NSB, NKC = G::NKC, NDT = G::NDT, LDK = G::LDA, LDV = G::LDA, SEG = MK_SEG<NKC>;
   __shared__ __attribute__((aligned(16))) float Ks[KB * LDK];
   __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
   [[maybe_unused]] float* Lw = nullptr;  // log w of the block's keys
@@ -416,9 +422,14 @@ __global__ __launch_bounds__(256) void masked_attn_dq_kernel(const float* __rest
     for (int sb = 0; sb < NSB; ++sb) {
       f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kc = 0; kc < NKC; ++kc) {
-        st = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], st);
-        dpt = mk_mfma(Vs[(16 * sb + c) * LDV + 4 * kc + g], Gq[kc], dpt);
+      for (int k0 = 0; k0 < NKC; k0 += SEG) {  // (the score in the forward kernel's segments)
+        f32x4 part = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kc = k0; kc < k0 + SEG; ++kc) {
+          part = mk_mfma(Ks[(16 * sb + c) * LDK + 4 * kc + g], Qq[kc], part);
+          dpt = mk_mfma(Vs[(16 * sb + c) * LDV + 4 * kc + g], Gq[kc], dpt);
+        }
+        st = k0 == 0 ? part : st + part;
       }
       [[maybe_unused]] f32x4 lw;
       if constexpr (WGT) lw = *(const f32x4*)(Lw + 16 * sb + 4 * g);
@@ -457,7 +468,7 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
                                                              float* __restrict__ dK, float* __restrict__ dV, float* __restrict__ dW,
                                                              int n_keys, int T, int Fp, int d, float scale) {
   using G = MkGeom<DP>;
-  constexpr int NKC = G::NKC, NDT = G::NDT, LD = G::LDA;
+  constexpr int NKC = G::NKC, NDT = G::NDT, LD = G::LDA, SEG = MK_SEG<NKC>;
   __shared__ __attribute__((aligned(16))) float Ks[16 * LD];
   __shared__ __attribute__((aligned(16))) float Vs[16 * LD];
   __shared__ f32x4 red[3 * 64];
@@ -512,13 +523,18 @@ __global__ __launch_bounds__(256) void masked_attn_dkv_kernel(const float* __res
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
     f32x4 dd = {0.f, 0.f, 0.f, 0.f};  // dO O^T [row = query 4 g + i][column = query c]: D on its diagonal, summed as dP is
 #pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      const bool ok = live && 4 * kc < d;
-      const size_t at = mk_pt(b, tilesT, Fp, ok ? q : 0, ok ? 4 * kc : 0) + g;
-      const float qv = ok ? Q[at] : 0.f, gv = ok ? dO[at] : 0.f;
-      dd = mk_mfma(gv, ok ? O[at] : 0.f, dd);
-      s = mk_mfma(qv, Ks[c * LD + 4 * kc + g], s);
-      dp = mk_mfma(gv, Vs[c * LD + 4 * kc + g], dp);
+    for (int k0 = 0; k0 < NKC; k0 += SEG) {  // (the score in the forward kernel's segments)
+      f32x4 part = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = k0; kc < k0 + SEG; ++kc) {
+        const bool ok = live && 4 * kc < d;
+        const size_t at = mk_pt(b, tilesT, Fp, ok ? q : 0, ok ? 4 * kc : 0) + g;
+        const float qv = ok ? Q[at] : 0.f, gv = ok ? dO[at] : 0.f;
+        dd = mk_mfma(gv, ok ? O[at] : 0.f, dd);
+        part = mk_mfma(qv, Ks[c * LD + 4 * kc + g], part);
+        dp = mk_mfma(gv, Vs[c * LD + 4 * kc + g], dp);
+      }
+      s = k0 == 0 ? part : s + part;
     }
     const float Lc = live ? lse[(size_t)b * T + q] : 0.f;
     f32x4 pr, ds;
