@@ -397,7 +397,36 @@ def _no_bf16_masked():
         raise NotImplementedError("per-task context counts (n_valid / n_cntxt) are not implemented in the bf16 compute mode")
 
 
-class PrefixTail:
+class KeyRule:
+    """What travels in the place of ``n_valid`` on the padded route: which keys the queries of every task attend over.  A rule is the
+    one place that knows how it attends -- ``attend(q_pt, k_pt, v_pt, n_keys, n_queries, d, scale, n_q_valid)`` makes its one
+    ``functional`` call on PT32 operands, the tasks being those of ``q_pt`` -- and which tasks have a key at all: ``live(n_tasks)``,
+    bool [n_tasks], computed on the device.  ``per_head(H, B, C)`` is the rule of the H * B head tasks ``h * B + b`` of a
+    ``MultiheadAttender``: counts repeated per head, weights expanded."""
+
+
+def as_key_rule(n_valid):
+    """A bare count tensor means its first keys; a rule passes through."""
+    return n_valid if isinstance(n_valid, KeyRule) else FirstKeys(n_valid)
+
+
+class FirstKeys(KeyRule):
+    """The first ``n_valid[b]`` of every task's keys (``functional.masked_attention``, the training route)."""
+
+    def __init__(self, n_valid):
+        self.n_valid = n_valid
+
+    def attend(self, q_pt, k_pt, v_pt, n_keys, n_queries, d, scale, n_q_valid):
+        return FN.masked_attention(q_pt, k_pt, v_pt, self.n_valid, q_pt.shape[0], n_keys, n_queries, d, scale, n_q_valid=n_q_valid)
+
+    def live(self, n_tasks):
+        return self.n_valid > 0
+
+    def per_head(self, H, B, C):
+        return FirstKeys(FN.counts_i32(self.n_valid, B).repeat(H))
+
+
+class PrefixTail(KeyRule):
     """The keys / values of ``n_tasks = S * n_prefix_tasks`` tasks as two segments (``functional.masked_attention_prefix``): a prefix
     shared by the S tasks ``j, j + n_prefix_tasks, ...`` (``k_pre`` / ``v_pre`` PT32 [n_prefix_tasks, c_pad, .], counts ``n_pre``) and a
     tail of every task's own (``k_tail`` / ``v_tail`` PT32 [n_tasks, m_tail, .], counts ``n_tail``).  Handed to ``attend_pt`` in the
@@ -408,19 +437,45 @@ class PrefixTail:
         self.k_pre, self.v_pre, self.n_pre, self.k_tail, self.v_tail, self.n_tail = k_pre, v_pre, n_pre, k_tail, v_tail, n_tail
         self.n_prefix_tasks, self.c_pad, self.m_tail, self.heads_of_prefix = n_prefix_tasks, c_pad, m_tail, heads_of_prefix
 
+    def attend(self, q_pt, k_pt, v_pt, n_keys, n_queries, d, scale, n_q_valid):
+        """(``k_pt`` / ``v_pt`` are not read: the tensors travel with the counts.)"""
+        return FN.masked_attention_prefix(q_pt, self.k_pre, self.v_pre, self.n_pre, self.k_tail, self.v_tail, self.n_tail, q_pt.shape[0],
+                                          self.n_prefix_tasks, self.c_pad, self.m_tail, n_queries, d, scale, n_q_valid=n_q_valid)
+
     def live(self, n_tasks):
         """bool [n_tasks]: does the task have a key in either segment (``n_tasks`` = S * the tasks the counts were given for)."""
         B = self.n_pre.shape[0]
         return ((self.n_pre.clamp(0, self.c_pad).repeat(n_tasks // B) + self.n_tail.clamp(0, self.m_tail)) > 0)
 
+    def per_head_tails(self, H, B, k_tail, v_tail):
+        """The rule of the S * H * B0 head tasks in sample-major order (task ``s * (B0 H) + h * B0 + b``, so that the kernel's
+        ``j % (B0 H)`` is the prefix task) over the tails ``k_tail`` / ``v_tail`` split and laid out likewise: the prefix as stored
+        (already split), its counts repeated per head, the tail counts of the ``B = S * B0`` tasks expanded per head."""
+        B0 = self.n_prefix_tasks // H
+        S = B // B0
+        n_tail = FN.counts_i32(self.n_tail, B, "n_tail").view(S, 1, B0).expand(S, H, B0).reshape(S * H * B0)
+        return PrefixTail(self.k_pre, self.v_pre, FN.counts_i32(self.n_pre, B0, "n_pre").repeat(H), k_tail, v_tail, n_tail, H * B0,
+                          self.c_pad, self.m_tail)
 
-class LeaveOneOut:
+
+class LeaveOneOut(KeyRule):
     """The key counts ``n_valid`` of a padded batch with the request that query row ``t`` of a task shall not see key row ``t`` of that
     task (``functional.masked_attention_loo``): the queries are the context points themselves, each attends over the others.
     Handed to ``attend_pt`` in the place of ``n_valid``, inference only."""
 
     def __init__(self, n_valid):
         self.n_valid = n_valid
+
+    def attend(self, q_pt, k_pt, v_pt, n_keys, n_queries, d, scale, n_q_valid):
+        return FN.masked_attention_loo(q_pt, k_pt, v_pt, self.n_valid, q_pt.shape[0], n_keys, n_queries, d, scale, n_q_valid=n_q_valid)
+
+    def live(self, n_tasks):
+        """(The targets are the context points: a task needs two of them to have a key left.)"""
+        return self.n_valid > 1
+
+    def per_head(self, H, B, C):
+        """(The row numbers of a head task are those of its task.)"""
+        return LeaveOneOut(FN.counts_i32(self.n_valid, B).repeat(H))
 
 
 def _has_admissible_key(w, n_valid, n_tasks):
@@ -432,7 +487,7 @@ def _has_admissible_key(w, n_valid, n_tasks):
     return ((w > 0) & (w < math.inf) & below).any(dim=1)
 
 
-class KeyWeights:
+class KeyWeights(KeyRule):
     """The key counts ``n_valid`` [B] of a padded batch with a non-negative weight per (replicate, task, key), ``w`` float [S, B, C]
     (``functional.masked_attention_weighted``): the ``S * B`` tasks handed to ``attend_pt`` are S replicates of the B context tasks in
     replicate-major order (task ``s * B + b``), all attending over the ONE stored copy of the B tasks' keys / values, replicate ``s``
@@ -444,12 +499,24 @@ class KeyWeights:
     def __init__(self, w, n_valid, S):
         self.w, self.n_valid, self.S = w, n_valid, int(S)
 
+    def attend(self, q_pt, k_pt, v_pt, n_keys, n_queries, d, scale, n_q_valid):
+        B0 = self.n_valid.shape[0]  # (the queries and their counts are shared by the replicates: those of the first one are read)
+        return FN.masked_attention_weighted(q_pt[:B0], k_pt, v_pt, self.w, self.n_valid, self.S * B0, B0, n_keys, n_queries, d, scale,
+                                            n_q_valid=None if n_q_valid is None else n_q_valid[:B0])
+
     def live(self, n_tasks):
         """bool [n_tasks]: does the replicate task have an admissible key (computed on the device, no host read)."""
         return _has_admissible_key(self.w, self.n_valid.repeat(self.S), n_tasks)
 
+    def per_head(self, H, B, C):
+        """The rule over the H * B0 stored head tasks ``h * B0 + b`` (``B = S * B0``): the weights expanded to [S, H, B0, C], so that
+        row ``s * (B0 H) + h * B0 + b`` is replicate ``s`` of that head task."""
+        S, B0 = self.S, B // self.S
+        w = FN.key_weights(self.w, B, C).view(S, 1, B0, C).expand(S, H, B0, C).contiguous()
+        return KeyWeights(w, FN.counts_i32(self.n_valid, B0).repeat(H), S)
 
-class TrainKeyWeights:
+
+class TrainKeyWeights(KeyRule):
     """The key counts ``n_valid`` [B] of a padded batch with a weight per (task, key), ``w`` float [B, C], on the TRAINING route
     (``functional.key_weighted_attention``): one replicate, every task attends over its own keys with ``p_k ~ w[b, k] exp(s_k)``, and
     the call is differentiable in queries, keys, values and ``w`` (which may require grad).  Handed to ``attend_pt`` in the place of
@@ -459,9 +526,18 @@ class TrainKeyWeights:
     def __init__(self, w, n_valid):
         self.w, self.n_valid = w, n_valid
 
+    def attend(self, q_pt, k_pt, v_pt, n_keys, n_queries, d, scale, n_q_valid):
+        return FN.key_weighted_attention(q_pt, k_pt, v_pt, self.w, self.n_valid, q_pt.shape[0], n_keys, n_queries, d, scale,
+                                         n_q_valid=n_q_valid)
+
     def live(self, n_tasks):
         """bool [n_tasks]: does the task have an admissible key (computed on the device, no host read, no gradient)."""
         return _has_admissible_key(self.w.detach(), self.n_valid, n_tasks)
+
+    def per_head(self, H, B, C):
+        """(Head task h * B + b reads the weights of task b; the expansion is an autograd op, so d w sums over the heads.)"""
+        w = FN.key_weights(self.w, B, C, detach=False).unsqueeze(0).expand(H, B, C).reshape(H * B, C)
+        return TrainKeyWeights(w, FN.counts_i32(self.n_valid, B).repeat(H))
 
 
 def _sample_major(x, S, H, B):
@@ -511,38 +587,17 @@ class DotAttender(nn.Module):
         attention_long.py beyond).  ``n_valid``: device integer tensor [n_tasks], the number of real keys of every task among
         the ``n_keys`` rows (a padded batch): the masked attention kernel (``functional.masked_attention``).  ``n_q_valid`` (with
         ``n_valid`` only): the number of real queries of every task; the rows beyond come back as zeros and are skipped.
-        ``n_valid`` as a :class:`LeaveOneOut`: the same with query row ``t`` kept from key row ``t`` (inference only); as a
-        :class:`TrainKeyWeights`: the same with a weight per key, differentiable in the weights too (``forward(w_cntxt=...)``)."""
+        ``n_valid`` as another :class:`KeyRule`: that rule's call -- a :class:`LeaveOneOut` keeps query row ``t`` from key row ``t``
+        (inference only), a :class:`TrainKeyWeights` weighs every key and is differentiable in the weights too
+        (``forward(w_cntxt=...)``), a :class:`KeyWeights` or :class:`PrefixTail` serves ``Conditioned``."""
         from .attention_long import long_scaledot_attention
 
         if n_q_valid is not None and n_valid is None:
             raise NotImplementedError("n_q_valid needs n_valid: query counts are an option of the masked attention kernel")
-        if isinstance(n_valid, PrefixTail):  # (a shared prefix and an own tail per task: Conditioned.sample_functions)
-            _no_bf16_masked()
-            w, scale = n_valid, 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
-            return FN.masked_attention_prefix(queries_pt, w.k_pre, w.v_pre, w.n_pre, w.k_tail, w.v_tail, w.n_tail, queries_pt.shape[0],
-                                              w.n_prefix_tasks, w.c_pad, w.m_tail, n_queries, self.kq_size, scale, n_q_valid=n_q_valid)
-        if isinstance(n_valid, LeaveOneOut):  # (query row t without key row t: NeuralProcessFamily.loo)
+        if n_valid is not None:  # (a padded batch: the rule makes its own masked-attention call)
             _no_bf16_masked()
             scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
-            return FN.masked_attention_loo(queries_pt, keys_pt, values_pt, n_valid.n_valid, queries_pt.shape[0], n_keys, n_queries,
-                                           self.kq_size, scale, n_q_valid=n_q_valid)
-        if isinstance(n_valid, KeyWeights):  # (S replicates of one stored context, a weight per key: Conditioned.reweighted)
-            _no_bf16_masked()
-            kw, scale = n_valid, 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
-            B0 = kw.n_valid.shape[0]  # (the queries and their counts are shared by the replicates: those of the first one are read)
-            return FN.masked_attention_weighted(queries_pt[:B0], keys_pt, values_pt, kw.w, kw.n_valid, kw.S * B0, B0, n_keys, n_queries,
-                                                self.kq_size, scale, n_q_valid=None if n_q_valid is None else n_q_valid[:B0])
-        if isinstance(n_valid, TrainKeyWeights):  # (a weight per key of every task's own context, with gradients: forward(w_cntxt=...))
-            _no_bf16_masked()
-            scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
-            return FN.key_weighted_attention(queries_pt, keys_pt, values_pt, n_valid.w, n_valid.n_valid, queries_pt.shape[0], n_keys,
-                                             n_queries, self.kq_size, scale, n_q_valid=n_q_valid)
-        if n_valid is not None:
-            _no_bf16_masked()
-            scale = 1.0 / math.sqrt(self.kq_size) if self.is_scale else 1.0
-            return FN.masked_attention(queries_pt, keys_pt, values_pt, n_valid, queries_pt.shape[0], n_keys, n_queries,
-                                       self.kq_size, scale, n_q_valid=n_q_valid)
+            return as_key_rule(n_valid).attend(queries_pt, keys_pt, values_pt, n_keys, n_queries, self.kq_size, scale, n_q_valid)
         if self.fits_fused(n_keys):
             ch = Chain(queries_pt.shape[0], n_queries, queries_pt.device, wg_per_task=True)
             ch.input_pt(queries_pt, self.kq_size)
@@ -637,22 +692,17 @@ class MultiheadAttender(nn.Module):
             S = B // B0
             Qp = queries_proj if queries_proj is not None else self._project(queries_pt, B, T, self.query_transform)
             Qh, Kt, Vt = (_sample_major(FN.split_heads(x, B, n, d, H), S, H, B0) for x, n in ((Qp, T), (w.k_tail, w.m_tail), (w.v_tail, w.m_tail)))
-            n_tail = FN.counts_i32(w.n_tail, B, "n_tail").view(S, 1, B0).expand(S, H, B0).reshape(S * H * B0)
-            heads = PrefixTail(w.k_pre, w.v_pre, FN.counts_i32(w.n_pre, B0, "n_pre").repeat(H), Kt, Vt, n_tail, H * B0, w.c_pad, w.m_tail)
-            Oh = self.dot.attend_pt(Qh, None, None, C, T, n_valid=heads)
+            Oh = self.dot.attend_pt(Qh, None, None, C, T, n_valid=w.per_head_tails(H, B, Kt, Vt))
             return FN.merge_heads(_head_major(Oh, S, H, B0), B, T, self.value_size, H)
         if isinstance(n_valid, KeyWeights):
             # heads as tasks over one stored context: keys / values projected and split ONCE (task h * B0 + b), the shared queries
-            # likewise; the weights are expanded per head to [S, H, B0, C] so that row s * (B0 H) + h * B0 + b is replicate s of
-            # head task h * B0 + b, and the result goes back head-major for the merge
+            # likewise; the rule's weights go per head in sample-major order, and the result goes back head-major for the merge
             _no_bf16_masked()
-            kw = n_valid
-            S, B0 = kw.S, B // kw.S
+            S, B0 = n_valid.S, B // n_valid.S
             Kh = FN.split_heads(self._project(keys_pt, B0, C, self.key_transform), B0, C, d, H)
             Vh = FN.split_heads(self._project(values_pt, B0, C, self.value_transform), B0, C, self.value_size, H)
             Qh = FN.split_heads(self._project(queries_pt[:B0], B0, T, self.query_transform), B0, T, d, H)
-            w = FN.key_weights_f32(kw.w, B, C).view(S, 1, B0, C).expand(S, H, B0, C).contiguous()
-            heads = KeyWeights(w, FN.counts_i32(kw.n_valid, B0).repeat(H), S)
+            heads = n_valid.per_head(H, B, C)
             nq = None if n_q_valid is None else FN.counts_i32(n_q_valid, B, "n_q_valid")[:B0].repeat(H)
             Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=heads, n_q_valid=nq)
             return FN.merge_heads(_head_major(Oh, S, H, B0), B, T, self.value_size, H)
@@ -662,16 +712,8 @@ class MultiheadAttender(nn.Module):
             Qp = queries_proj if queries_proj is not None else self._project(queries_pt, B, T, self.query_transform)
             Qh = FN.split_heads(Qp, B, T, d, H)
             Vh = FN.split_heads(self._project(values_pt, B, C, self.value_transform), B, C, self.value_size, H)
-            if isinstance(n_valid, LeaveOneOut):  # (the same route on the leave-one-out launch: the row numbers are those of the task)
-                counts = LeaveOneOut(FN.counts_i32(n_valid.n_valid, B).repeat(H))
-            elif isinstance(n_valid, TrainKeyWeights):
-                # (the same route on the key-weighted training kernels: head task h * B + b reads the weights of task b; the
-                # expansion is an autograd op, so d w sums over the heads)
-                w = FN.key_weights_grad(n_valid.w, B, C).unsqueeze(0).expand(H, B, C).reshape(H * B, C)
-                counts = TrainKeyWeights(w, FN.counts_i32(n_valid.n_valid, B).repeat(H))
-            else:
-                counts = FN.counts_i32(n_valid, B).repeat(H)
-            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=counts,
+            heads = as_key_rule(n_valid).per_head(H, B, C)
+            Oh = self.dot.attend_pt(Qh, Kh, Vh, C, T, n_valid=heads,
                                     n_q_valid=None if n_q_valid is None else FN.counts_i32(n_q_valid, B, "n_q_valid").repeat(H))
             return FN.merge_heads(Oh, B, T, self.value_size, H)
         if FN.mha_usable(self.kq_head_size, self.value_head_size, C):

@@ -26,6 +26,26 @@ from . import _lib as L
 # bench.py sets this to a list to time every launch with HIP events on the launch stream:
 # entries are (kernel, algorithmic flops, start event, end event, algorithmic HBM bytes)
 PROFILE = None
+
+
+def profile_begin() -> Optional[torch.cuda.Event]:
+    """The start event of one launch, recorded on the launch stream; None while nobody profiles."""
+    if PROFILE is None:
+        return None
+    ev0 = torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    return ev0
+
+
+def profile_end(ev0: Optional[torch.cuda.Event], name: str, flops: int, nbytes: int, what: str) -> None:
+    """Close the bracket ``profile_begin`` opened: one PROFILE entry with a trailing note."""
+    if ev0 is None:
+        return
+    ev1 = torch.cuda.Event(enable_timing=True)
+    ev1.record()
+    PROFILE.append((name, flops, ev0, ev1, nbytes, what))
+
+
 # tests set this to a list: every chain execution then leaves a record of the tensors it read and wrote -- ("fwd", chain,
 # inputs, saved tensors by (step, role), outputs, bf16) and ("bwd", chain, incoming gradients, buffers by (step, role), wgrad
 # jobs, bf16) -- so that a test can check each step against the kernel's OWN stored inputs (tests/teacher.py)

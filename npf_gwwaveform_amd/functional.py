@@ -10,6 +10,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib as L
+from . import chain as CH
 from .chain import pad32, pt_empty, pt_shape, tiles_of
 
 
@@ -643,8 +644,6 @@ class _MhaFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_pt, k_pt, v_pt, n_tasks, n_keys, n_queries, n_heads, head):
-        from . import chain as CH
-
         F = n_heads * head
         q_pt, k_pt, v_pt = q_pt.contiguous(), k_pt.contiguous(), v_pt.contiguous()
         train = any(ctx.needs_input_grad[:3])
@@ -652,15 +651,11 @@ class _MhaFn(torch.autograd.Function):
         whole = F % 32 == 0 and n_queries % 32 == 0
         out = (torch.empty if whole else torch.zeros)(CH.pt_shape(n_tasks, n_queries, F), dtype=torch.float32, device=q_pt.device)
         lse = torch.empty((n_tasks, n_heads, n_queries), dtype=torch.float32, device=q_pt.device) if train else None
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        ev0 = CH.profile_begin()
         L.check(L.load().npf_mha_fwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), n_tasks, n_heads, n_keys, n_queries, F, L.ptr(out),
                                      L.ptr(lse) if lse is not None else None, L.stream_ptr()), "npf_mha_fwd")
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("mha_fwd_kernel", 4 * n_tasks * n_queries * n_keys * F, ev0, ev1,
-                               4 * F * n_tasks * (2 * n_queries + 2 * n_keys), "multihead attention"))
+        CH.profile_end(ev0, "mha_fwd_kernel", 4 * n_tasks * n_queries * n_keys * F, 4 * F * n_tasks * (2 * n_queries + 2 * n_keys),
+                       "multihead attention")
         ctx.geom = (n_tasks, n_keys, n_queries, n_heads, F)
         if train:
             ctx.save_for_backward(q_pt, k_pt, v_pt, out, lse)
@@ -668,23 +663,17 @@ class _MhaFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import chain as CH
-
         n_tasks, n_keys, n_queries, n_heads, F = ctx.geom
         q_pt, k_pt, v_pt, out, lse = ctx.saved_tensors
         g = g.contiguous()
         # (zeros where the kernel leaves something unwritten, as in the forward pass)
         mk = lambda t, n: (torch.empty_like if (F % 32 == 0 and n % 32 == 0) else torch.zeros_like)(t)  # noqa: E731
         dq, dk, dv = mk(q_pt, n_queries), mk(k_pt, n_keys), mk(v_pt, n_keys)
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        ev0 = CH.profile_begin()
         L.check(L.load().npf_mha_bwd(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(out), L.ptr(g), L.ptr(lse), n_tasks, n_heads,
                                      n_keys, n_queries, F, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.stream_ptr()), "npf_mha_bwd")
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("mha_bwd_kernel", 14 * n_tasks * n_queries * n_keys * F, ev0, ev1,
-                               4 * F * n_tasks * (4 * n_queries + 4 * n_keys), "multihead attention backward"))
+        CH.profile_end(ev0, "mha_bwd_kernel", 14 * n_tasks * n_queries * n_keys * F, 4 * F * n_tasks * (4 * n_queries + 4 * n_keys),
+                       "multihead attention backward")
         return dq, dk, dv, None, None, None, None, None
 
 
@@ -710,22 +699,16 @@ class _AddLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a_pt, b_pt, gamma, beta, eps, n_tasks, pts, F):
-        from . import chain as CH
-
         a_pt, b_pt = a_pt.contiguous(), b_pt.contiguous()
         tiles = tiles_of(pts)
         train = any(ctx.needs_input_grad[:4])
         y = (torch.zeros if pad32(F) != F else torch.empty)(CH.pt_shape(n_tasks, pts, F), dtype=torch.float32, device=a_pt.device)
         stats = torch.empty((n_tasks * tiles * 32, 2), dtype=torch.float32, device=a_pt.device) if train else None
         g, bt = gamma.detach().contiguous(), beta.detach().contiguous()
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        ev0 = CH.profile_begin()
         L.check(L.load().npf_add_layernorm_fwd(L.ptr(a_pt), L.ptr(b_pt), L.ptr(g), L.ptr(bt), float(eps), n_tasks, pts, F, L.ptr(y),
                                                L.ptr(stats) if stats is not None else None, L.stream_ptr()), "npf_add_layernorm_fwd")
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("add_layernorm_fwd_kernel", 0, ev0, ev1, 12 * n_tasks * tiles * 32 * F, "LayerNorm(a + b)"))
+        CH.profile_end(ev0, "add_layernorm_fwd_kernel", 0, 12 * n_tasks * tiles * 32 * F, "LayerNorm(a + b)")
         ctx.geom = (n_tasks, pts, F, tiles)
         if train:
             ctx.save_for_backward(a_pt, b_pt, g, stats)
@@ -733,22 +716,16 @@ class _AddLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from . import chain as CH
-
         n_tasks, pts, F, tiles = ctx.geom
         a_pt, b_pt, g, stats = ctx.saved_tensors
         dy = dy.contiguous()
         dx = (torch.zeros if pad32(F) != F else torch.empty)(CH.pt_shape(n_tasks, pts, F), dtype=torch.float32, device=dy.device)
         partials = torch.empty((n_tasks * tiles, 2, F), dtype=torch.float32, device=dy.device)
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        ev0 = CH.profile_begin()
         L.check(L.load().npf_add_layernorm_bwd(L.ptr(a_pt), L.ptr(b_pt), L.ptr(g), L.ptr(stats), L.ptr(dy), n_tasks, pts, F, L.ptr(dx),
                                                L.ptr(partials), L.stream_ptr()), "npf_add_layernorm_bwd")
         sums = partials.sum(0)
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("add_layernorm_bwd_kernel", 0, ev0, ev1, 16 * n_tasks * tiles * 32 * F, "LayerNorm(a + b) backward"))
+        CH.profile_end(ev0, "add_layernorm_bwd_kernel", 0, 16 * n_tasks * tiles * 32 * F, "LayerNorm(a + b) backward")
         return dx, dx, sums[0], sums[1], None, None, None, None
 
 
@@ -782,59 +759,121 @@ def counts_i32(n_valid: torch.Tensor, n_tasks: int, what: str = "n_valid") -> to
     return n_valid.to(torch.int32).contiguous()
 
 
+def _query_counts(n_q_valid: Optional[torch.Tensor], n_tasks: int) -> Optional[torch.Tensor]:
+    return None if n_q_valid is None else counts_i32(n_q_valid, n_tasks, "n_q_valid")
+
+
 def _iptr(t: torch.Tensor) -> int:
     assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
     return t.data_ptr()
 
 
+# ---- the refusals the wrappers below share (every wrapper keeps its own selection and order) -----------------------------------
+def _check_width(d):
+    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
+        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
+
+
+def _check_sizes(**sizes):
+    if any(v < 0 for v in sizes.values()):
+        raise ValueError("negative size: " + ", ".join(f"{name}={v}" for name, v in sizes.items()))
+
+
+def _check_replicates(n_tasks, n_src, src_name, reads):
+    if n_src < 1 or n_tasks < 0 or n_tasks % n_src != 0:
+        raise ValueError(f"n_tasks={n_tasks} must be a multiple of {src_name}={n_src} >= 1 (task j reads {reads} j % {src_name})")
+
+
+def _check_pt32(what, t, n_tasks, pts, F, any_type=False):
+    """Refuse ``t`` unless it is an fp32 PT32 tensor [n_tasks, pts, F].  ``any_type``: ``t`` may be no tensor at all (the
+    differentiable wrappers, whose message then names its type)."""
+    shape = tuple(pt_shape(n_tasks, pts, F))
+    if any_type and not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {shape}, got {type(t).__name__}")
+    if tuple(t.shape) != shape or t.dtype != torch.float32:
+        got = (t.dtype, tuple(t.shape)) if any_type else f"{t.dtype} {tuple(t.shape)}"
+        raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {shape}, got {got}")
+
+
+def _inference_operands(who, operands, F, w=None):
+    """The PT32 operands ``(what, tensor, tasks, points)`` of an inference-only wrapper, detached and contiguous: refused where one
+    of them (or the weights ``w``) requires grad, or is no fp32 PT32 tensor [tasks, points, F]."""
+    if any(t.requires_grad for _, t, _, _ in operands) or (isinstance(w, torch.Tensor) and w.requires_grad):
+        raise RuntimeError(f"{who} is inference only (no backward pass): detach the inputs")
+    for what, t, n_tasks, pts in operands:
+        _check_pt32(what, t, n_tasks, pts, F)
+    return [t.detach().contiguous() for _, t, _, _ in operands]
+
+
+def _attend_no_grad(entry, q_pt, keys, n_q_valid, sizes, n_queries, d, scale):
+    """PT32 [sizes[0], n_queries, d] from a forward-only entry point ``entry(q, *keys, n_q_valid, *sizes, n_queries, d, scale, out,
+    stream)``: ``keys`` are the entry's key-side pointers, ``sizes`` its task and key sizes, both in its own order."""
+    out = torch.empty(pt_shape(sizes[0], n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
+    L.check(getattr(L.load(), entry)(L.ptr(q_pt), *keys, _iptr(n_q_valid) if n_q_valid is not None else None, *sizes, n_queries, d,
+                                     float(scale), L.ptr(out), L.stream_ptr()), entry)
+    return out
+
+
+# PROFILE names and notes of _MaskedAttnFn, without / with key weights
+_MASKED_FWD_PROFILE = (("masked_attn_fwd_kernel", "masked attention (flops at full counts)"),
+                       ("masked_attn_fwd_weighted_kernel", "key-weighted attention (flops at full counts)"))
+_MASKED_BWD_PROFILE = (("masked_attn_bwd_kernels", "masked attention backward (flops at full counts)"),
+                       ("masked_attn_bwd_weighted_kernels", "key-weighted attention backward (flops at full counts)"))
+
+
 class _MaskedAttnFn(torch.autograd.Function):
     """out[b, q] = softmax over the first n_valid[b] keys of scale <Q[b, q], K[b, k]> times V on PT32 tensors (``npf_masked_attn_fwd`` /
-    ``_bwd``; DotAttender.forward, npf/architectures/attention.py:129-164,204-220, of the batch cut per task)."""
+    ``_bwd``; DotAttender.forward, npf/architectures/attention.py:129-164,204-220, of the batch cut per task).  With ``w`` (else
+    None) a weight per (task, key): ``p_k ~ w_k exp(s_k)`` (``npf_masked_attn_fwd_weighted`` / ``_fwd_weighted_ex`` at one
+    replicate, ``npf_masked_attn_bwd_weighted``), differentiable in q, k, v and w."""
 
     @staticmethod
-    def forward(ctx, q_pt, k_pt, v_pt, n_valid, n_tasks, n_keys, n_queries, d, scale, n_q_valid=None):
-        from . import chain as CH
-
+    def forward(ctx, q_pt, k_pt, v_pt, w, n_valid, n_tasks, n_keys, n_queries, d, scale, n_q_valid):
         q_pt, k_pt, v_pt = q_pt.contiguous(), k_pt.contiguous(), v_pt.contiguous()
-        train = any(ctx.needs_input_grad[:3])
-        out = torch.empty(CH.pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
+        train = any(ctx.needs_input_grad[:4])
+        out = torch.empty(pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
         lse = torch.empty((n_tasks, n_queries), dtype=torch.float32, device=q_pt.device) if train else None
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        # (n_q_valid: padded queries as well, the instances that skip them)
-        name, q_counts = ("npf_masked_attn_fwd", ()) if n_q_valid is None else ("npf_masked_attn_fwd_nq", (_iptr(n_q_valid),))
-        L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), *q_counts, n_tasks, n_keys, n_queries, d,
-                                        float(scale), L.ptr(out), L.ptr(lse) if lse is not None else None, L.stream_ptr()), name)
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("masked_attn_fwd_kernel", 4 * n_tasks * n_queries * n_keys * d, ev0, ev1,
-                               4 * pad32(d) * n_tasks * (2 * n_queries + 2 * n_keys), "masked attention (flops at full counts)"))
+        ev0 = CH.profile_begin()
+        if w is None:
+            # (n_q_valid: padded queries as well, the instances that skip them)
+            name, q_counts = ("npf_masked_attn_fwd", ()) if n_q_valid is None else ("npf_masked_attn_fwd_nq", (_iptr(n_q_valid),))
+            L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), *q_counts, n_tasks, n_keys, n_queries,
+                                            d, float(scale), L.ptr(out), L.ptr(lse) if lse is not None else None, L.stream_ptr()), name)
+        else:
+            w = w.contiguous()
+            name, keep = ("npf_masked_attn_fwd_weighted", ()) if lse is None else ("npf_masked_attn_fwd_weighted_ex", (L.ptr(lse),))
+            L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
+                                            _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks, n_tasks, n_keys, n_queries, d,
+                                            float(scale), L.ptr(out), *keep, L.stream_ptr()), name)
+        CH.profile_end(ev0, _MASKED_FWD_PROFILE[w is not None][0], 4 * n_tasks * n_queries * n_keys * d,
+                       4 * pad32(d) * n_tasks * (2 * n_queries + 2 * n_keys), _MASKED_FWD_PROFILE[w is not None][1])
         ctx.geom = (n_tasks, n_keys, n_queries, d, float(scale))
-        ctx.has_nq = n_q_valid is not None
         if train:
-            ctx.save_for_backward(q_pt, k_pt, v_pt, n_valid, out, lse, *((n_q_valid,) if ctx.has_nq else ()))
+            ctx.save_for_backward(q_pt, k_pt, v_pt, w, n_valid, out, lse, n_q_valid)
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        from . import chain as CH
-
         n_tasks, n_keys, n_queries, d, scale = ctx.geom
-        q_pt, k_pt, v_pt, n_valid, out, lse = ctx.saved_tensors[:6]
+        q_pt, k_pt, v_pt, w, n_valid, out, lse, n_q_valid = ctx.saved_tensors
         g = g.contiguous()
         dq, dk, dv = torch.empty_like(q_pt), torch.empty_like(k_pt), torch.empty_like(v_pt)  # (written whole)
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        name, q_counts = ("npf_masked_attn_bwd_nq", (_iptr(ctx.saved_tensors[6]),)) if ctx.has_nq else ("npf_masked_attn_bwd", ())
-        L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), *q_counts, L.ptr(out), L.ptr(g), L.ptr(lse),
-                                        n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.stream_ptr()), name)
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("masked_attn_bwd_kernels", 16 * n_tasks * n_queries * n_keys * d, ev0, ev1,
-                               4 * pad32(d) * n_tasks * (6 * n_queries + 4 * n_keys), "masked attention backward (flops at full counts)"))
-        return dq, dk, dv, None, None, None, None, None, None, None
+        dw = None if w is None else torch.empty_like(w)
+        ev0 = CH.profile_begin()
+        if w is None:
+            name, q_counts = ("npf_masked_attn_bwd", ()) if n_q_valid is None else ("npf_masked_attn_bwd_nq", (_iptr(n_q_valid),))
+            L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid), *q_counts, L.ptr(out), L.ptr(g),
+                                            L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk), L.ptr(dv),
+                                            L.stream_ptr()), name)
+        else:
+            L.check(L.load().npf_masked_attn_bwd_weighted(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
+                                                          _iptr(n_q_valid) if n_q_valid is not None else None, L.ptr(out), L.ptr(g),
+                                                          L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk),
+                                                          L.ptr(dv), L.ptr(dw), L.stream_ptr()), "npf_masked_attn_bwd_weighted")
+        CH.profile_end(ev0, _MASKED_BWD_PROFILE[w is not None][0], 16 * n_tasks * n_queries * n_keys * d,
+                       4 * pad32(d) * n_tasks * (6 * n_queries + 4 * n_keys), _MASKED_BWD_PROFILE[w is not None][1])
+        return dq, dk, dv, dw, None, None, None, None, None, None, None
 
 
 def masked_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, n_keys: int,
@@ -845,11 +884,9 @@ def masked_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor,
     ``n_q_valid``: the same for the queries (padded targets): the rows of the result at and beyond ``n_q_valid[task]`` are zeros, the
     queries there are never read and get a zero gradient, and the kernels skip them (``npf_masked_attn_fwd_nq`` / ``_bwd_nq``); the
     rows below the counts are bit-identical to the call without it."""
-    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
-        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
-    if n_q_valid is not None:
-        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
-    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale, n_q_valid)
+    _check_width(d)
+    n_q_valid = _query_counts(n_q_valid, n_tasks)
+    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, None, counts_i32(n_valid, n_tasks), n_tasks, n_keys, n_queries, d, scale, n_q_valid)
 
 
 def masked_attention_prefix(q_pt: torch.Tensor, k_pre: torch.Tensor, v_pre: torch.Tensor, n_prefix: torch.Tensor, k_tail: torch.Tensor,
@@ -861,32 +898,16 @@ def masked_attention_prefix(q_pt: torch.Tensor, k_pre: torch.Tensor, v_pre: torc
     zeros where both counts are 0 (``npf_masked_attn_fwd_prefix``).  Counts and ``n_q_valid`` as in :func:`masked_attention`: device
     int32 / int64, read by the kernel only.  Inference only -- there is no backward pass, and a call in which an input requires grad
     is refused."""
-    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
-        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
-    if n_prefix_tasks < 1 or n_tasks < 0 or n_tasks % n_prefix_tasks != 0:
-        raise ValueError(f"n_tasks={n_tasks} must be a multiple of n_prefix_tasks={n_prefix_tasks} >= 1 (task j reads prefix j % n_prefix_tasks)")
-    if c_pad < 0 or m_tail < 0 or n_queries < 0:
-        raise ValueError(f"negative size: c_pad={c_pad}, m_tail={m_tail}, n_queries={n_queries}")
-    tensors = (q_pt, k_pre, v_pre, k_tail, v_tail)
-    if any(t.requires_grad for t in tensors):
-        raise RuntimeError("masked_attention_prefix is inference only (no backward pass): detach the inputs")
-    from .chain import pt_shape
-
-    for what, t, shape in (("q_pt", q_pt, pt_shape(n_tasks, n_queries, d)), ("k_pre", k_pre, pt_shape(n_prefix_tasks, c_pad, d)),
-                           ("v_pre", v_pre, pt_shape(n_prefix_tasks, c_pad, d)), ("k_tail", k_tail, pt_shape(n_tasks, m_tail, d)),
-                           ("v_tail", v_tail, pt_shape(n_tasks, m_tail, d))):
-        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
-            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    _check_width(d)
+    _check_replicates(n_tasks, n_prefix_tasks, "n_prefix_tasks", "prefix")
+    _check_sizes(c_pad=c_pad, m_tail=m_tail, n_queries=n_queries)
+    q_pt, k_pre, v_pre, k_tail, v_tail = _inference_operands("masked_attention_prefix", (
+        ("q_pt", q_pt, n_tasks, n_queries), ("k_pre", k_pre, n_prefix_tasks, c_pad), ("v_pre", v_pre, n_prefix_tasks, c_pad),
+        ("k_tail", k_tail, n_tasks, m_tail), ("v_tail", v_tail, n_tasks, m_tail)), d)
     n_prefix, n_tail = counts_i32(n_prefix, n_prefix_tasks, "n_prefix"), counts_i32(n_tail, n_tasks, "n_tail")
-    if n_q_valid is not None:
-        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
-    q_pt, k_pre, v_pre, k_tail, v_tail = (t.detach().contiguous() for t in tensors)
-    out = torch.empty(pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
-    L.check(L.load().npf_masked_attn_fwd_prefix(L.ptr(q_pt), L.ptr(k_pre), L.ptr(v_pre), _iptr(n_prefix), L.ptr(k_tail), L.ptr(v_tail),
-                                                _iptr(n_tail), _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks,
-                                                n_prefix_tasks, c_pad, m_tail, n_queries, d, float(scale), L.ptr(out), L.stream_ptr()),
-            "npf_masked_attn_fwd_prefix")
-    return out
+    n_q_valid = _query_counts(n_q_valid, n_tasks)
+    keys = (L.ptr(k_pre), L.ptr(v_pre), _iptr(n_prefix), L.ptr(k_tail), L.ptr(v_tail), _iptr(n_tail))
+    return _attend_no_grad("npf_masked_attn_fwd_prefix", q_pt, keys, n_q_valid, (n_tasks, n_prefix_tasks, c_pad, m_tail), n_queries, d, scale)
 
 
 def masked_attention_loo(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, n_keys: int,
@@ -896,26 +917,14 @@ def masked_attention_loo(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Ten
     OTHER points of its task.  Exact zeros where no other key is left (a task with one point or none) and beyond ``n_q_valid``;
     ``v_pt`` row ``t`` has no influence on row ``t`` of the result.  Counts as in :func:`masked_attention`: device int32 / int64, read
     by the kernel only.  Inference only -- there is no backward pass, and a call in which an input requires grad is refused."""
-    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
-        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
-    if n_tasks < 0 or n_keys < 0 or n_queries < 0:
-        raise ValueError(f"negative size: n_tasks={n_tasks}, n_keys={n_keys}, n_queries={n_queries}")
-    tensors = (q_pt, k_pt, v_pt)
-    if any(t.requires_grad for t in tensors):
-        raise RuntimeError("masked_attention_loo is inference only (no backward pass): detach the inputs")
-    for what, t, shape in (("q_pt", q_pt, pt_shape(n_tasks, n_queries, d)), ("k_pt", k_pt, pt_shape(n_tasks, n_keys, d)),
-                           ("v_pt", v_pt, pt_shape(n_tasks, n_keys, d))):
-        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
-            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    _check_width(d)
+    _check_sizes(n_tasks=n_tasks, n_keys=n_keys, n_queries=n_queries)
+    q_pt, k_pt, v_pt = _inference_operands("masked_attention_loo", (
+        ("q_pt", q_pt, n_tasks, n_queries), ("k_pt", k_pt, n_tasks, n_keys), ("v_pt", v_pt, n_tasks, n_keys)), d)
     n_valid = counts_i32(n_valid, n_tasks)
-    if n_q_valid is not None:
-        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
-    q_pt, k_pt, v_pt = (t.detach().contiguous() for t in tensors)
-    out = torch.empty(pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
-    L.check(L.load().npf_masked_attn_fwd_loo(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid),
-                                             _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks, n_keys, n_queries, d,
-                                             float(scale), L.ptr(out), L.stream_ptr()), "npf_masked_attn_fwd_loo")
-    return out
+    n_q_valid = _query_counts(n_q_valid, n_tasks)
+    keys = (L.ptr(k_pt), L.ptr(v_pt), _iptr(n_valid))
+    return _attend_no_grad("npf_masked_attn_fwd_loo", q_pt, keys, n_q_valid, (n_tasks, n_keys), n_queries, d, scale)
 
 
 def loo_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, F: int) -> torch.Tensor:
@@ -928,8 +937,7 @@ def loo_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, 
         raise ValueError(f"loo_mean needs n_tasks >= 0, pts >= 1 and F >= 1, got {n_tasks}, {pts}, {F}")
     if R_pt.requires_grad:
         raise RuntimeError("loo_mean is inference only (no backward pass): detach the input")
-    if tuple(R_pt.shape) != tuple(pt_shape(n_tasks, pts, F)) or R_pt.dtype != torch.float32:
-        raise ValueError(f"R_pt must be an fp32 PT32 tensor of shape {tuple(pt_shape(n_tasks, pts, F))}, got {R_pt.dtype} {tuple(R_pt.shape)}")
+    _check_pt32("R_pt", R_pt, n_tasks, pts, F)
     n_valid = counts_i32(n_valid, n_tasks)
     R_pt = R_pt.detach().contiguous()
     out = torch.empty_like(R_pt)  # (written whole)
@@ -937,10 +945,11 @@ def loo_mean(R_pt: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, pts: int, 
     return out
 
 
-def key_weights_f32(w: torch.Tensor, n_tasks: int, n_keys: int, what: str = "w") -> torch.Tensor:
-    """The per-(task, key) weights as the contiguous device fp32 [n_tasks, n_keys] tensor the reweighting kernels read: any float
+def key_weights(w: torch.Tensor, n_tasks: int, n_keys: int, what: str = "w", detach: bool = True) -> torch.Tensor:
+    """The per-(task, key) weights as the contiguous device fp32 [n_tasks, n_keys] tensor the weighted kernels read: any float
     tensor with ``n_tasks * n_keys`` elements whose leading dims multiply to ``n_tasks``; a contiguous fp32 tensor is used as given
-    (a view, no copy), so weights overwritten in place are seen by a replayed graph.  The values are never read by the host."""
+    (a view, no copy), so weights overwritten in place are seen by a replayed graph.  The values are never read by the host.
+    ``detach=False`` (the training route): the tensor stays in the autograd graph."""
     if not isinstance(w, torch.Tensor) or not w.is_floating_point():
         raise ValueError(f"{what} must be a float device tensor [..., {n_keys}] with {n_tasks} rows, got "
                          f"{w.dtype if isinstance(w, torch.Tensor) else type(w).__name__}")
@@ -948,7 +957,7 @@ def key_weights_f32(w: torch.Tensor, n_tasks: int, n_keys: int, what: str = "w")
         raise ValueError(f"{what} must hold one weight per (task, key): {n_tasks} rows of {n_keys}, got {list(w.shape)}")
     if not w.is_cuda:
         raise ValueError(f"{what} must live on the device (its values are read by the kernels, never by the host)")
-    return w.detach().to(torch.float32).contiguous().view(n_tasks, n_keys)
+    return (w.detach() if detach else w).to(torch.float32).contiguous().view(n_tasks, n_keys)
 
 
 def masked_attention_weighted(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor,
@@ -962,29 +971,16 @@ def masked_attention_weighted(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torc
     the key, an integer weight is "the point appears w times".  Exact zeros where no key is admissible and beyond ``n_q_valid``; with
     every weight 1.0 and one replicate the bits of :func:`masked_attention`.  Counts and weights are read by the kernel only.
     Inference only -- there is no backward pass, and a call in which an input requires grad is refused."""
-    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
-        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
-    if n_ctx_tasks < 1 or n_tasks < 0 or n_tasks % n_ctx_tasks != 0:
-        raise ValueError(f"n_tasks={n_tasks} must be a multiple of n_ctx_tasks={n_ctx_tasks} >= 1 (task j reads context task j % n_ctx_tasks)")
-    if n_keys < 0 or n_queries < 0:
-        raise ValueError(f"negative size: n_keys={n_keys}, n_queries={n_queries}")
-    tensors = (q_pt, k_pt, v_pt)
-    if any(t.requires_grad for t in tensors) or (isinstance(w, torch.Tensor) and w.requires_grad):
-        raise RuntimeError("masked_attention_weighted is inference only (no backward pass): detach the inputs")
-    for what, t, shape in (("q_pt", q_pt, pt_shape(n_ctx_tasks, n_queries, d)), ("k_pt", k_pt, pt_shape(n_ctx_tasks, n_keys, d)),
-                           ("v_pt", v_pt, pt_shape(n_ctx_tasks, n_keys, d))):
-        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
-            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    w = key_weights_f32(w, n_tasks, n_keys)
+    _check_width(d)
+    _check_replicates(n_tasks, n_ctx_tasks, "n_ctx_tasks", "context task")
+    _check_sizes(n_keys=n_keys, n_queries=n_queries)
+    q_pt, k_pt, v_pt = _inference_operands("masked_attention_weighted", (
+        ("q_pt", q_pt, n_ctx_tasks, n_queries), ("k_pt", k_pt, n_ctx_tasks, n_keys), ("v_pt", v_pt, n_ctx_tasks, n_keys)), d, w)
+    w = key_weights(w, n_tasks, n_keys)
     n_valid = counts_i32(n_valid, n_ctx_tasks)
-    if n_q_valid is not None:
-        n_q_valid = counts_i32(n_q_valid, n_ctx_tasks, "n_q_valid")
-    q_pt, k_pt, v_pt = (t.detach().contiguous() for t in tensors)
-    out = torch.empty(pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
-    L.check(L.load().npf_masked_attn_fwd_weighted(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
-                                                  _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks, n_ctx_tasks, n_keys,
-                                                  n_queries, d, float(scale), L.ptr(out), L.stream_ptr()), "npf_masked_attn_fwd_weighted")
-    return out
+    n_q_valid = _query_counts(n_q_valid, n_ctx_tasks)
+    keys = (L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid))
+    return _attend_no_grad("npf_masked_attn_fwd_weighted", q_pt, keys, n_q_valid, (n_tasks, n_ctx_tasks, n_keys), n_queries, d, scale)
 
 
 def weighted_mean(R_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor, n_tasks: int, n_ctx_tasks: int, pts: int,
@@ -994,17 +990,12 @@ def weighted_mean(R_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor, n_
     [n_ctx_tasks, pts, F], zeros where the admissible weights sum to 0 (``npf_weighted_mean``: sums and division in double, one
     rounding, fixed order).  ``w``: float [n_tasks, pts] (or [S, n_ctx_tasks, pts]).  Counts and weights as in
     :func:`masked_attention_weighted`.  Inference only: a call in which an input requires grad is refused."""
-    if n_ctx_tasks < 1 or n_tasks < 0 or n_tasks % n_ctx_tasks != 0:
-        raise ValueError(f"n_tasks={n_tasks} must be a multiple of n_ctx_tasks={n_ctx_tasks} >= 1 (task j reads context task j % n_ctx_tasks)")
+    _check_replicates(n_tasks, n_ctx_tasks, "n_ctx_tasks", "context task")
     if pts < 1 or F < 1:
         raise ValueError(f"weighted_mean needs pts >= 1 and F >= 1, got {pts}, {F}")
-    if R_pt.requires_grad or (isinstance(w, torch.Tensor) and w.requires_grad):
-        raise RuntimeError("weighted_mean is inference only (no backward pass): detach the inputs")
-    if tuple(R_pt.shape) != tuple(pt_shape(n_ctx_tasks, pts, F)) or R_pt.dtype != torch.float32:
-        raise ValueError(f"R_pt must be an fp32 PT32 tensor of shape {tuple(pt_shape(n_ctx_tasks, pts, F))}, got {R_pt.dtype} {tuple(R_pt.shape)}")
-    w = key_weights_f32(w, n_tasks, pts)
+    (R_pt,) = _inference_operands("weighted_mean", (("R_pt", R_pt, n_ctx_tasks, pts),), F, w)
+    w = key_weights(w, n_tasks, pts)
     n_valid = counts_i32(n_valid, n_ctx_tasks)
-    R_pt = R_pt.detach().contiguous()
     out = torch.empty((n_tasks, pad32(F)), dtype=torch.float32, device=R_pt.device)  # (written whole)
     L.check(L.load().npf_weighted_mean(L.ptr(R_pt), L.ptr(w), _iptr(n_valid), n_tasks, n_ctx_tasks, pts, pad32(F), L.ptr(out),
                                        L.stream_ptr()), "npf_weighted_mean")
@@ -1012,72 +1003,6 @@ def weighted_mean(R_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor, n_
 
 
 # ---- training through key weights (npf_masked_attn_fwd_weighted_ex / _bwd_weighted, npf_weighted_mean_bwd) -------------------
-def key_weights_grad(w: torch.Tensor, n_tasks: int, n_keys: int, what: str = "w") -> torch.Tensor:
-    """:func:`key_weights_f32` for the training route: the same checks, but the tensor stays in the autograd graph (no detach); a
-    contiguous fp32 [n_tasks, n_keys] tensor is used as given, so weights overwritten in place are seen by a replayed graph."""
-    if not isinstance(w, torch.Tensor) or not w.is_floating_point():
-        raise ValueError(f"{what} must be a float device tensor [..., {n_keys}] with {n_tasks} rows, got "
-                         f"{w.dtype if isinstance(w, torch.Tensor) else type(w).__name__}")
-    if w.dim() < 2 or w.shape[-1] != n_keys or w.numel() != n_tasks * n_keys:
-        raise ValueError(f"{what} must hold one weight per (task, key): {n_tasks} rows of {n_keys}, got {list(w.shape)}")
-    if not w.is_cuda:
-        raise ValueError(f"{what} must live on the device (its values are read by the kernels, never by the host)")
-    return w.to(torch.float32).contiguous().view(n_tasks, n_keys)
-
-
-class _KeyWeightedAttnFn(torch.autograd.Function):
-    """:class:`_MaskedAttnFn` with a weight per (task, key): ``p_k ~ w_k exp(s_k)`` (``npf_masked_attn_fwd_weighted`` /
-    ``_fwd_weighted_ex`` at one replicate, ``npf_masked_attn_bwd_weighted``), differentiable in q, k, v and w."""
-
-    @staticmethod
-    def forward(ctx, q_pt, k_pt, v_pt, w, n_valid, n_tasks, n_keys, n_queries, d, scale, n_q_valid=None):
-        from . import chain as CH
-
-        q_pt, k_pt, v_pt, w = q_pt.contiguous(), k_pt.contiguous(), v_pt.contiguous(), w.contiguous()
-        train = any(ctx.needs_input_grad[:4])
-        out = torch.empty(CH.pt_shape(n_tasks, n_queries, d), dtype=torch.float32, device=q_pt.device)  # (written whole)
-        lse = torch.empty((n_tasks, n_queries), dtype=torch.float32, device=q_pt.device) if train else None
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        name, keep = ("npf_masked_attn_fwd_weighted", ()) if lse is None else ("npf_masked_attn_fwd_weighted_ex", (L.ptr(lse),))
-        L.check(getattr(L.load(), name)(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
-                                        _iptr(n_q_valid) if n_q_valid is not None else None, n_tasks, n_tasks, n_keys, n_queries, d,
-                                        float(scale), L.ptr(out), *keep, L.stream_ptr()), name)
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("masked_attn_fwd_weighted_kernel", 4 * n_tasks * n_queries * n_keys * d, ev0, ev1,
-                               4 * pad32(d) * n_tasks * (2 * n_queries + 2 * n_keys), "key-weighted attention (flops at full counts)"))
-        ctx.geom = (n_tasks, n_keys, n_queries, d, float(scale))
-        ctx.has_nq = n_q_valid is not None
-        if train:
-            ctx.save_for_backward(q_pt, k_pt, v_pt, w, n_valid, out, lse, *((n_q_valid,) if ctx.has_nq else ()))
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        from . import chain as CH
-
-        n_tasks, n_keys, n_queries, d, scale = ctx.geom
-        q_pt, k_pt, v_pt, w, n_valid, out, lse = ctx.saved_tensors[:7]
-        g = g.contiguous()
-        dq, dk, dv, dw = torch.empty_like(q_pt), torch.empty_like(k_pt), torch.empty_like(v_pt), torch.empty_like(w)  # (written whole)
-        if CH.PROFILE is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        L.check(L.load().npf_masked_attn_bwd_weighted(L.ptr(q_pt), L.ptr(k_pt), L.ptr(v_pt), L.ptr(w), _iptr(n_valid),
-                                                      _iptr(ctx.saved_tensors[7]) if ctx.has_nq else None, L.ptr(out), L.ptr(g),
-                                                      L.ptr(lse), n_tasks, n_keys, n_queries, d, scale, L.ptr(dq), L.ptr(dk),
-                                                      L.ptr(dv), L.ptr(dw), L.stream_ptr()), "npf_masked_attn_bwd_weighted")
-        if CH.PROFILE is not None:
-            ev1.record()
-            CH.PROFILE.append(("masked_attn_bwd_weighted_kernels", 16 * n_tasks * n_queries * n_keys * d, ev0, ev1,
-                               4 * pad32(d) * n_tasks * (6 * n_queries + 4 * n_keys),
-                               "key-weighted attention backward (flops at full counts)"))
-        return dq, dk, dv, dw, None, None, None, None, None, None, None
-
-
 def key_weighted_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor,
                            n_tasks: int, n_keys: int, n_queries: int, d: int, scale: float,
                            n_q_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1091,20 +1016,13 @@ def key_weighted_attention(q_pt: torch.Tensor, k_pt: torch.Tensor, v_pt: torch.T
     needed (``npf_masked_attn_fwd_weighted_ex``, else ``npf_masked_attn_fwd_weighted``); the backward pass is one
     ``npf_masked_attn_bwd_weighted`` call (two launches, no atomics, every output written whole).  Counts, ``n_q_valid`` and weights
     are read by the kernels only: no host sync, and a captured call sees weights overwritten in place.  No double backward."""
-    if d % 4 != 0 or not 0 < d <= MASKED_MAX_WIDTH:
-        raise NotImplementedError(f"masked attention takes feature widths that are multiples of 4 up to {MASKED_MAX_WIDTH}, got {d}")
-    if n_tasks < 0 or n_keys < 0 or n_queries < 0:
-        raise ValueError(f"negative size: n_tasks={n_tasks}, n_keys={n_keys}, n_queries={n_queries}")
-    for what, t, shape in (("q_pt", q_pt, pt_shape(n_tasks, n_queries, d)), ("k_pt", k_pt, pt_shape(n_tasks, n_keys, d)),
-                           ("v_pt", v_pt, pt_shape(n_tasks, n_keys, d))):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
-            raise ValueError(f"{what} must be an fp32 PT32 tensor of shape {tuple(shape)}, got "
-                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
-    w = key_weights_grad(w, n_tasks, n_keys)
+    _check_width(d)
+    _check_sizes(n_tasks=n_tasks, n_keys=n_keys, n_queries=n_queries)
+    for what, t, pts in (("q_pt", q_pt, n_queries), ("k_pt", k_pt, n_keys), ("v_pt", v_pt, n_keys)):
+        _check_pt32(what, t, n_tasks, pts, d, any_type=True)
+    w = key_weights(w, n_tasks, n_keys, detach=False)
     n_valid = counts_i32(n_valid, n_tasks)
-    if n_q_valid is not None:
-        n_q_valid = counts_i32(n_q_valid, n_tasks, "n_q_valid")
-    return _KeyWeightedAttnFn.apply(q_pt, k_pt, v_pt, w, n_valid, n_tasks, n_keys, n_queries, d, scale, n_q_valid)
+    return _MaskedAttnFn.apply(q_pt, k_pt, v_pt, w, n_valid, n_tasks, n_keys, n_queries, d, scale, _query_counts(n_q_valid, n_tasks))
 
 
 class _KeyWeightedMeanFn(torch.autograd.Function):
@@ -1144,10 +1062,8 @@ def key_weighted_mean(R_pt: torch.Tensor, w: torch.Tensor, n_valid: torch.Tensor
     its rows repeated.  Counts and weights are read by the kernels only.  No double backward."""
     if n_tasks < 0 or pts < 1 or F < 1:
         raise ValueError(f"key_weighted_mean needs n_tasks >= 0, pts >= 1 and F >= 1, got {n_tasks}, {pts}, {F}")
-    if not isinstance(R_pt, torch.Tensor) or tuple(R_pt.shape) != tuple(pt_shape(n_tasks, pts, F)) or R_pt.dtype != torch.float32:
-        raise ValueError(f"R_pt must be an fp32 PT32 tensor of shape {tuple(pt_shape(n_tasks, pts, F))}, got "
-                         f"{(R_pt.dtype, tuple(R_pt.shape)) if isinstance(R_pt, torch.Tensor) else type(R_pt).__name__}")
-    w = key_weights_grad(w, n_tasks, pts)
+    _check_pt32("R_pt", R_pt, n_tasks, pts, F, any_type=True)
+    w = key_weights(w, n_tasks, pts, detach=False)
     return _KeyWeightedMeanFn.apply(R_pt, w, counts_i32(n_valid, n_tasks), n_tasks, pts, F)
 
 

@@ -27,7 +27,7 @@ from torch.distributions import Independent, Normal
 
 from . import functional as FN
 from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlatInputs, MultiheadAttender, PrefixTail, SelfAttention,
-                            TrainKeyWeights, get_attender, merge_flat_input)
+                            TrainKeyWeights, as_key_rule, get_attender, merge_flat_input)
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
@@ -1568,19 +1568,9 @@ class AttnCNP(NeuralProcessFamily):
         on the batch cut per task).  A task without context gets zeros, as ``trgt_dependent_representation`` at C = 0 -- also
         behind an attender whose learned layers would turn zero context vectors into something else.  ``n_q_valid``: the target
         sizes of a batch whose targets are padded too; the attention skips the queries beyond them."""
-        if isinstance(n_valid, PrefixTail):  # (two key segments per task, Conditioned.sample_functions: the tensors travel with the counts)
-            R_t = self.attender.attend_pt(Xt_pt.t, None, None, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
-            live = n_valid.live(B)
-        elif isinstance(n_valid, LeaveOneOut):  # (the targets are the context points: a task needs two of them to have a key left)
-            R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
-            live = n_valid.n_valid > 1
-        elif isinstance(n_valid, (KeyWeights, TrainKeyWeights)):
-            # (KeyWeights: B = S replicates x the stored tasks; either way a task needs one key of positive weight)
-            R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
-            live = n_valid.live(B)
-        else:
-            R_t = self.attender.attend_pt(Xt_pt.t, Xc_pt.t, R.t, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
-            live = n_valid > 0
+        k_pt, v_pt = (None, None) if Xc_pt is None else (Xc_pt.t, R.t)  # (a PrefixTail carries its own keys / values)
+        R_t = self.attender.attend_pt(Xt_pt.t, k_pt, v_pt, C, T, n_valid=n_valid, n_q_valid=n_q_valid)
+        live = as_key_rule(n_valid).live(B)
         if not isinstance(self.attender, DotAttender):
             R_t = R_t * live.to(R_t.dtype).view(B, 1, 1, 1, 1)
         return R_t
