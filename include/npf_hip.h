@@ -26,6 +26,8 @@
  *                        predicted amplitude and phase (training on the mismatch; no reference counterpart)
  *   npf_waveform_loglike  matched-filter SNR and log likelihood of complex data under the predicted waveforms, phase and arrival
  *                        time maximised or marginalised, and marginal over the latent samples (inference; no reference counterpart)
+ *   npf_waveform_loglike_net  the coherent likelihood of a detector network: per-detector weights, delays and complex responses,
+ *                        the complex correlations added before the modulus (inference; no reference counterpart)
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -791,6 +793,53 @@ int npf_waveform_loglike(const float *h, int32_t h_ld, const float *d, const flo
                          double dtau, int32_t n_tau, double *hh, double *dd, double *snr, double *lnl_max, double *lnl_marg,
                          int32_t *tau_index, double *phase, double *series, double *lnl_mix, double *lnl_max_mix, void *workspace,
                          void *stream);
+
+/* ---- coherent matched-filter log likelihood of a detector network (csrc/waveform_net_kernels.hip; no reference counterpart)
+ * h, h_ld, freq, freq_rows, n_valid, n_rows, n_tasks, pts, tau0, dtau, n_tau, the rows r = s * n_tasks + b: as in
+ * npf_waveform_loglike.  Detector k < n_det = D, 1 <= D <= NPF_NET_MAX_DET, sees the same waveform with its own noise spectrum, its own
+ * arrival delay and its own complex response factor (antenna pattern times inclination):
+ *   d[n_tasks][D][pts][2]     fp32, the data of every task and detector as (Re, Im)
+ *   wgt                       fp32, [D][pts] (wgt_rows == 1) or [n_tasks][D][pts] (wgt_rows == n_tasks), NULL: ones
+ *   delay[n_tasks][D]         DOUBLE, DEVICE data: seconds, either sign, not tied to the grid; NULL: zeros
+ *   resp[n_tasks][D][2]       DOUBLE, DEVICE data: C_{b,k} = (Re, Im); detector k's template is C_k h shifted by tau_j + delay_k
+ * The host reads neither delay nor resp: both may be overwritten in place between the replays of a captured graph.
+ * A point is LIVE FOR DETECTOR k if t < n_valid[b] and 0 < w_{k,t} < +inf; nothing is read of a point that is not live, in any of that
+ * detector's arrays (NaN included).  freq is shared by the detectors and is read only for points that are live for at least one
+ * detector.  All sums run over the live points, in double, from fp32 inputs widened exactly:
+ *   kappa_{k,j} = sum_t w_{k,t} A_t e^{i (phi_t + 2 pi f_t (tau_j + delay_k))} conj(d_{k,t})       tau_j = tau0 + j dtau, j < n_tau
+ *   hh_k = sum_t w_{k,t} A_t^2          dd_k = sum_t w_{k,t} |d_{k,t}|^2
+ *   K_j  = sum_k C_k kappa_{k,j}        HH = sum_k |C_k|^2 hh_k        DD = sum_k dd_k        (k in ascending order)
+ *   x_j  = |K_j|                        j* = the smallest j that attains max_j x_j
+ *   snr      = x_{j*} / sqrt(HH)        phase = arg K_{j*}             lnl_max = x_{j*} - HH / 2
+ *   L_j      = ln I0(x_j) - HH / 2      lnl_marg = logsumexp_j L_j - ln n,  n = max(n_tau, 1)
+ *   lnl_mix[b], lnl_max_mix[b]: the log-mean-exp of lnl_marg / lnl_max over the latent samples, as in npf_waveform_loglike
+ *   snr_det[r][k] = |kappa_{k,j*}| / sqrt(hh_k)   (0 where hh_k == 0)      hh_det[r][k] = hh_k      dd_det[b][k] = dd_k
+ * The complex sums of the detectors are added BEFORE the modulus is taken: one coalescence phase and one geocentric arrival time are
+ * shared by the network, which D calls of npf_waveform_loglike cannot give.  n_tau == 0: the one candidate is tau = 0 and the delays
+ * still enter, so freq is required whenever delay is given (with neither a grid nor delays freq is not read and may be NULL).  A
+ * degenerate row, HH == 0 (no live point, a zero template or no response), gets the zeros npf_waveform_loglike gives, and its
+ * snr_det is taken at j* = 0.  A detector with C_k == 0 changes no network output and still reports its snr_det.  ln I0, its switch
+ * point and both max-shifted log-sum-exps are those of npf_waveform_loglike.
+ * Launch 1: one workgroup per (row, chunk of NPF_WAVEFORM_JC shifts) walks the detectors; per detector the recurrence and the
+ * reduction order of npf_waveform_loglike's first launch (one double sincos of phi + 2 pi f (tau_c0 + delay_k) and one of the step per
+ * live point, restarted at every chunk), and the reducing threads add C_k kappa_{k,j} to the network sums in ascending k.  The sums a
+ * thread keeps do not grow with D.  Launch 2: one workgroup per task walks its n_z rows in order over the network sums and, for
+ * snr_det, forms the D sums kappa_{k,j*} once more at the single shift j* (a direct sincos per live point): no per-detector series is
+ * kept.  No atomics: a second call on the same inputs gives the same bits; the host reads nothing, so the call sits in a captured graph.
+ * Outputs, all DOUBLE but tau_index (each may be NULL, at least one must be given; every requested element is written):
+ * hh (= HH) / snr / lnl_max / lnl_marg / tau_index / phase [n_rows], dd (= DD) / lnl_mix / lnl_max_mix [n_tasks],
+ * series[n_rows][max(n_tau, 1)][2] = (L_j, x_j / sqrt(HH)), hh_det / snr_det [n_rows][D], dd_det [n_tasks][D].
+ * workspace: npf_waveform_loglike_net_workspace_bytes(n_rows, n_det, n_tau) bytes of device memory, 8-byte aligned: per row 2 + 2 D
+ * doubles and whole chunks of (Re, Im) (-1 for sizes the call refuses).  Status: NPF_EINVAL (nothing launched) for everything
+ * npf_waveform_loglike refuses, n_det outside [1, NPF_NET_MAX_DET], a NULL resp, and delay given with a NULL freq. */
+#define NPF_NET_MAX_DET 8
+int64_t npf_waveform_loglike_net_workspace_bytes(int32_t n_rows, int32_t n_det, int32_t n_tau);
+int npf_waveform_loglike_net(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                             int32_t freq_rows, const int32_t *n_valid, const double *delay, const double *resp, int32_t n_rows,
+                             int32_t n_tasks, int32_t n_det, int32_t pts, double tau0, double dtau, int32_t n_tau, double *hh,
+                             double *dd, double *snr, double *lnl_max, double *lnl_marg, int32_t *tau_index, double *phase,
+                             double *series, double *lnl_mix, double *lnl_max_mix, double *hh_det, double *snr_det, double *dd_det,
+                             void *workspace, void *stream);
 
 int npf_version(void);
 

@@ -1,0 +1,67 @@
+// What waveform_kernels.hip and waveform_net_kernels.hip share: the launch geometry of the correlation launches, the fixed-order
+// workgroup sum and ln I0 in double.
+#pragma once
+#include "npf_common.hpp"
+
+namespace npf {
+
+constexpr int kWfJC = NPF_WAVEFORM_JC;  // time shifts per workgroup of launch 1
+constexpr int kWfThreads = 128;
+constexpr int kWfMaxTau = 65536;
+constexpr double kWfTwoPi = 6.283185307179586476925286766559;
+
+inline int wf_chunks(int n_tau) { return n_tau > 0 ? (n_tau + kWfJC - 1) / kWfJC : 1; }
+
+// dst[i] = sum over the workgroup of v[i], i < N (N <= THREADS): lanes by xor shuffles, then the waves in order.  red: N * waves doubles.
+template <int N, int THREADS>
+__device__ __forceinline__ void block_sum_store(double (&v)[N], double* red, double* __restrict__ dst) {
+  constexpr int WAVES = THREADS / 64;
+  static_assert(N <= THREADS, "one thread per sum");
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off);
+  }
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();  // red may still be read by a previous call
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[i * WAVES + wave] = v[i];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < N) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) s += red[threadIdx.x * WAVES + w];
+    dst[threadIdx.x] = s;
+  }
+}
+
+constexpr int kWfLlThreads = 256;  // threads of a finishing workgroup
+constexpr double kWfI0Switch = NPF_LOGLIKE_I0_SWITCH;
+constexpr int kWfI0AsymTerms = 16;   // terms of the 1 / (8 x) series above the switch: truncation 2.7e-16 of I0 at x = 24, less beyond
+constexpr int kWfI0PowerTerms = 48;  // cap of the power series below it (40 terms reach 2^-60 of the sum at x = 24)
+
+// ln I0(x), x >= 0, without overflow.  Below the switch point x_s = 24: log1p of the power series I0 - 1 = sum_{k >= 1} (x^2 / 4)^k /
+// (k!)^2 (positive terms: no cancellation, and log1p keeps the relative accuracy as x -> 0).  From x_s on:
+// x - ln(2 pi x) / 2 + log1p(S) with S = sum_{k = 1 .. 16} prod_{m <= k} (2 m - 1)^2 / (8 x m), summed by Horner's rule.
+__device__ __forceinline__ double wf_log_i0(double x) {
+  if (x < kWfI0Switch) {
+    const double q = 0.25 * x * x;
+    double t = q, s = q;
+#pragma unroll
+    for (int k = 2; k <= kWfI0PowerTerms; ++k) {
+      t *= q * (1.0 / (double)(k * k));  // (unrolled: the reciprocal is a constant, no division in the chain)
+      s += t;
+      if (t <= s * 0x1p-60) break;
+    }
+    return log1p(s);
+  }
+  const double u = 0.125 / x;
+  double acc = 0.0;
+#pragma unroll
+  for (int k = kWfI0AsymTerms; k >= 1; --k) acc = u * ((double)((2 * k - 1) * (2 * k - 1)) / (double)k) * (1.0 + acc);
+  return x - 0.5 * log(kWfTwoPi * x) + log1p(acc);
+}
+
+}  // namespace npf

@@ -561,6 +561,122 @@ def waveform_loglike(h: torch.Tensor, data: torch.Tensor, weights: Optional[torc
     return WaveformLogLike(*(out[name] for name in LOGLIKE_NAMES), ser)
 
 
+# ---- coherent matched-filter log likelihood of a detector network (csrc/waveform_net_kernels.hip) --------------
+NET_MAX_DET = 8  # NPF_NET_MAX_DET
+LOGLIKE_NET_NAMES = LOGLIKE_NAMES + ("hh_det", "snr_det", "dd_det")
+_LOGLIKE_NET_PER_DET = ("hh_det", "snr_det", "dd_det")
+
+
+class WaveformLogLikeNetwork(NamedTuple):
+    """What :func:`waveform_loglike_network` returns (float64 but ``tau_index``); the entries that were not asked for are ``None``."""
+    hh: Optional[torch.Tensor]           # [R] HH = sum_k |C_k|^2 hh_k: the optimal network SNR squared
+    dd: Optional[torch.Tensor]           # [B] DD = sum_k dd_k
+    snr: Optional[torch.Tensor]          # [R] max_j |K_j| / sqrt(HH)
+    lnl_max: Optional[torch.Tensor]      # [R] phase and time maximised
+    lnl_marg: Optional[torch.Tensor]     # [R] phase and time marginalised
+    tau_index: Optional[torch.Tensor]    # [R] int32
+    phase: Optional[torch.Tensor]        # [R]
+    lnl_mix: Optional[torch.Tensor]      # [B] lnl_marg marginalised over the latent samples
+    lnl_max_mix: Optional[torch.Tensor]  # [B] the same of lnl_max
+    hh_det: Optional[torch.Tensor]       # [R, D] hh_k = sum_t w_k A^2
+    snr_det: Optional[torch.Tensor]      # [R, D] |kappa_{k,j*}| / sqrt(hh_k) at the network's grid time
+    dd_det: Optional[torch.Tensor]       # [B, D] dd_k = sum_t w_k |d_k|^2
+    series: Optional[torch.Tensor]       # [R, max(n_tau, 1), 2] = (L_j, x_j / sqrt(HH))
+
+
+def check_loglike_network_args(h_shape, data, response, delays=None, weights=None, freqs=None, taus=None):
+    """The shapes, dtypes and host values of a :func:`waveform_loglike_network` call -> ``(R, T, h_ld, B, D, wgt_rows, freq_rows, tau0,
+    dtau, n_tau)``; ``ValueError`` for anything that does not fit.  Reads shapes and dtypes only, so it runs on tensors of any
+    device: ``h_shape`` = [R, T, >= 2], ``data`` [B, D, T, 2] with ``1 <= D <= NET_MAX_DET`` and ``R % B == 0``, ``response``
+    float64 [B, D, 2], ``delays`` ``None`` or float64 [B, D] (needs ``freqs``), ``weights`` ``None``, [D, T] or [B, D, T], ``freqs``
+    ``None``, [T] or [B, T], ``taus`` as in :func:`check_match_args`."""
+    h_shape = tuple(h_shape)
+    if len(h_shape) != 3 or h_shape[2] < 2 or h_shape[0] < 1 or h_shape[1] < 1:
+        raise ValueError(f"h must have shape [R, T, >= 2] (amplitude, phase first), got {list(h_shape)}")
+    R, T, ld = h_shape
+    shape_of = lambda t: list(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__  # noqa: E731
+    if not isinstance(data, torch.Tensor) or data.dim() != 4 or data.shape[0] < 1 or tuple(data.shape[2:]) != (T, 2):
+        raise ValueError(f"data = (Re, Im) per detector must have shape [B, D, T={T}, 2], got {shape_of(data)}")
+    B, D = data.shape[0], data.shape[1]
+    if not 1 <= D <= NET_MAX_DET:
+        raise ValueError(f"data holds {D} detectors: 1 <= D <= {NET_MAX_DET}")
+    if R % B != 0:
+        raise ValueError(f"h holds {R} rows, data {B} tasks: R % B != 0 (row k * B + b is latent sample k of task b)")
+    if not isinstance(response, torch.Tensor) or tuple(response.shape) != (B, D, 2) or response.dtype != torch.float64:
+        raise ValueError(f"response = (Re C, Im C) must be a float64 tensor of shape [B={B}, D={D}, 2], got {shape_of(response)}"
+                         f"{' of ' + str(response.dtype) if isinstance(response, torch.Tensor) else ''}")
+    if delays is not None and (not isinstance(delays, torch.Tensor) or tuple(delays.shape) != (B, D) or delays.dtype != torch.float64):
+        raise ValueError(f"delays (seconds) must be None or a float64 tensor of shape [B={B}, D={D}], got {shape_of(delays)}"
+                         f"{' of ' + str(delays.dtype) if isinstance(delays, torch.Tensor) else ''}")
+    if weights is not None and (not isinstance(weights, torch.Tensor) or tuple(weights.shape) not in ((D, T), (B, D, T))):
+        raise ValueError(f"weights must be None or a tensor of shape [D={D}, T={T}] or [B={B}, D={D}, T={T}], got {shape_of(weights)}")
+    if freqs is not None and (not isinstance(freqs, torch.Tensor) or tuple(freqs.shape) not in ((T,), (B, T))):
+        raise ValueError(f"freqs must be None or a tensor of shape [T={T}] or [B={B}, T={T}], got {shape_of(freqs)}")
+    if delays is not None and freqs is None:
+        raise ValueError("delays need freqs: a delay enters as the phase 2 pi f delay")
+    wgt_rows = 1 if weights is None or weights.dim() == 2 else B
+    freq_rows = 1 if freqs is None or freqs.dim() == 1 else B
+    taus = check_taus(taus, freqs is not None)
+    tau0, dtau, n_tau = taus if taus is not None else (0.0, 0.0, 0)
+    return R, T, ld, B, D, wgt_rows, freq_rows, tau0, dtau, n_tau
+
+
+def waveform_loglike_network(h: torch.Tensor, data: torch.Tensor, response: torch.Tensor, delays: Optional[torch.Tensor] = None,
+                             weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None, taus=None,
+                             n_valid: Optional[torch.Tensor] = None, want=LOGLIKE_NET_NAMES,
+                             series: bool = False) -> WaveformLogLikeNetwork:
+    """Coherent matched-filter SNR and log likelihood ratio of the data of a network of ``D`` detectors, ``data`` [B, D, T, 2] =
+    (Re d_k, Im d_k), under the predicted waveforms ``h`` [R, T, >= 2] (as in :func:`waveform_loglike`).  Detector ``k`` sees
+    ``C_k h`` shifted by ``tau_j + delay_k``: ``response`` [B, D, 2] = (Re C, Im C) and ``delays`` [B, D] (seconds, either sign, not
+    tied to the grid; ``None``: zeros) are float64 DEVICE tensors, taken as they are -- the host does not read them, so a captured
+    graph sees what they hold at replay.  With ``kappa_{k,j} = sum_t w_k A e^{i (phi + 2 pi f (tau_j + delay_k))} conj(d_k)`` the
+    network sums ``K_j = sum_k C_k kappa_{k,j}``, ``HH = sum_k |C_k|^2 hh_k``, ``DD = sum_k dd_k`` stand where ``kappa_j``, ``hh``,
+    ``dd`` stand in :func:`waveform_loglike`: the complex correlations are added before the modulus is taken, one phase and one
+    arrival time are shared by the detectors.  ``hh_det`` / ``dd_det`` are the detectors' own ``hh_k`` / ``dd_k`` and ``snr_det``
+    is ``|kappa_{k,j*}| / sqrt(hh_k)`` at the network's grid time; ``include/npf_hip.h`` has the contract and the edge cases.
+    ``weights``: [D, T] or [B, D, T] (``None``: ones); a point is removed per detector.  ``freqs`` ([T] or [B, T]) is shared by the
+    detectors and required with ``taus`` or ``delays``.  ``taus``, ``n_valid``, ``want`` (names out of ``LOGLIKE_NET_NAMES``),
+    ``series``: as in :func:`waveform_loglike`.  Two ``npf_waveform_loglike_net`` launches in double arithmetic, inference only,
+    no host sync, deterministic; the workspace is the one of :func:`waveform_match`."""
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or any(w not in LOGLIKE_NET_NAMES for w in want):
+        raise ValueError(f"want must be a tuple / list of names out of {LOGLIKE_NET_NAMES}, got {want!r}")
+    want = tuple(want)
+    R, T, ld, B, D, wgt_rows, freq_rows, tau0, dtau, n_tau = check_loglike_network_args(getattr(h, "shape", ()), data, response, delays,
+                                                                                        weights, freqs, taus)
+    if not want and not series:
+        raise ValueError(f"want must name at least one of {LOGLIKE_NET_NAMES} (or series=True)")
+    for t in (h, data, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    for t, what in ((response, "response"), (delays, "delays")):
+        if t is not None and (not t.is_cuda or t.device != h.device):
+            raise ValueError(f"{what} must live on the device of h ({h.device}), got {t.device}: the kernel reads it there")
+    h, data = h.detach().contiguous(), data.detach().contiguous()
+    response = response.detach().contiguous()
+    delays = delays.detach().contiguous() if delays is not None else None
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and (n_tau > 0 or delays is not None) else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    lib = L.load()
+    ws = _match_workspace(h.device, int(lib.npf_waveform_loglike_net_workspace_bytes(R, D, n_tau)))
+
+    def new(name):
+        rows = B if name in _LOGLIKE_PER_TASK or name == "dd_det" else R
+        return torch.empty((rows, D) if name in _LOGLIKE_NET_PER_DET else (rows,),
+                           dtype=torch.int32 if name == "tau_index" else torch.float64, device=h.device)
+
+    out = {name: (new(name) if name in want else None) for name in LOGLIKE_NET_NAMES}
+    ser = torch.empty((R, max(n_tau, 1), 2), dtype=torch.float64, device=h.device) if series else None
+    dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    per_row = [dptr(out[name]) for name in ("hh", "dd", "snr", "lnl_max", "lnl_marg", "tau_index", "phase")]
+    L.check(lib.npf_waveform_loglike_net(L.ptr(h), ld, L.ptr(data), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows,
+                                         _iptr(nv) if nv is not None else None, dptr(delays), dptr(response), R, B, D, T, tau0, dtau,
+                                         n_tau, *per_row, dptr(ser), dptr(out["lnl_mix"]), dptr(out["lnl_max_mix"]),
+                                         dptr(out["hh_det"]), dptr(out["snr_det"]), dptr(out["dd_det"]), ws.data_ptr(),
+                                         L.stream_ptr()), "npf_waveform_loglike_net")
+    return WaveformLogLikeNetwork(*(out[name] for name in LOGLIKE_NET_NAMES), ser)
+
+
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------
 MC_MEAN, MC_LOGMEANEXP, MC_SUMO = 0, 1, 2
 

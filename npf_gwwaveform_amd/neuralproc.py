@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlat
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "LogLike", "Reweighted", "bootstrap_weights",
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "LogLike", "NetworkLogLike", "Reweighted", "bootstrap_weights",
            "kfold_weights"]
 
 
@@ -85,6 +85,27 @@ class LogLike(NamedTuple):
     lnl_max_mix: torch.Tensor          # [B] the same of lnl_max
     dd: torch.Tensor                   # [B] <d|d>; ln L = ln Lambda - dd / 2 + const
     series: Optional[torch.Tensor]     # [.., B, max(n_tau, 1), 2] = (L_j, SNR_j) over the whole grid (``series=True``)
+
+
+class NetworkLogLike(NamedTuple):
+    """Coherent matched-filter likelihood of the data of a detector network under the predicted waveforms
+    (:meth:`HeadDistribution.loglike_network`), float64 (but ``tau_index``).  The fields of :class:`LogLike`, taken over the network
+    sums, plus the detectors' own shares.  Per (latent sample, task): [n_z, B] for ``of="samples"``, [1, B] for ``of="mean"``; per
+    task: [B]; per detector: a last axis of ``D``."""
+    optimal_snr: torch.Tensor          # sqrt(sum_k |C_k|^2 <h|h>_k): the optimal network SNR
+    snr: torch.Tensor                  # max over phase and grid times of |sum_k C_k <d_k|h>_k| / optimal_snr
+    lnl_max: torch.Tensor              # ln Lambda maximised over the shared phase and the grid times
+    lnl_marg: torch.Tensor             # ln Lambda marginalised over the shared phase and the grid times (uniform priors)
+    phase: torch.Tensor                # arg of the network sum at the maximum
+    tau: Optional[torch.Tensor]        # the (geocentric) grid time of the maximum (``taus`` given)
+    tau_index: Optional[torch.Tensor]  # int32: its index on the grid, the smallest one (``taus`` given)
+    lnl: torch.Tensor                  # [B] lnl_marg marginalised over the latent samples: log-mean-exp
+    lnl_max_mix: torch.Tensor          # [B] the same of lnl_max
+    dd: torch.Tensor                   # [B] sum_k <d_k|d_k>; ln L = ln Lambda - dd / 2 + const
+    series: Optional[torch.Tensor]     # [.., B, max(n_tau, 1), 2] = (L_j, SNR_j) over the whole grid (``series=True``)
+    snr_det: torch.Tensor              # [.., B, D] |<d_k|h>_k| / sqrt(<h|h>_k) at the network's grid time
+    optimal_snr_det: torch.Tensor      # [.., B, D] |C_k| sqrt(<h|h>_k)
+    dd_det: torch.Tensor               # [B, D] <d_k|d_k>
 
 
 class HeadDistribution(Independent):
@@ -220,6 +241,47 @@ class HeadDistribution(Independent):
             return LogLike(m.hh.sqrt().view(lead), m.snr.view(lead), m.lnl_max.view(lead), m.lnl_marg.view(lead), m.phase.view(lead),
                            tau, m.tau_index.view(lead) if taus is not None else None, m.lnl_mix, m.lnl_max_mix, m.dd,
                            m.series.view(*lead, *m.series.shape[1:]) if series else None)
+
+    def loglike_network(self, data, response, delays=None, weights=None, freqs=None, taus=None, of="samples",
+                        series=False) -> NetworkLogLike:
+        """The coherent matched-filter log likelihood ratio of the data of a network of ``D`` detectors, ``data`` [B, D, T, 2] =
+        (Re d_k, Im d_k), with the predicted waveform as the template -> :class:`NetworkLogLike`.  Detector ``k`` sees ``C_k h``
+        shifted by ``tau_j + delay_k`` under its own noise ``weights`` ([D, T] or [B, D, T]; ``None``: ones; a point whose weight is
+        not in (0, inf) is removed for that detector): ``response`` [B, D, 2] = (Re C, Im C), the antenna pattern times the
+        inclination factor, and ``delays`` [B, D] in seconds (either sign, not tied to the grid; ``None``: zeros) are float64 device
+        tensors the host never reads.  The detectors' complex correlations ``<d_k|h>_k`` are added, each times ``C_k``, BEFORE the
+        modulus is taken, and ``<h|h> = sum_k |C_k|^2 <h|h>_k``: one coalescence phase and one geocentric arrival time are shared by
+        the network, which ``D`` calls of :meth:`loglike` cannot give (they maximise per detector and add moduli).  Everything else --
+        ``freqs`` ([T] or [B, T], shared by the detectors, required with ``taus`` or ``delays``), ``taus``, ``of``, ``series``, the
+        marginal over the latent samples, padded targets (``n_trgt``), float64 results -- is as in :meth:`loglike`; ``snr_det`` is
+        each detector's own SNR at the network's grid time, ``optimal_snr_det = |C_k| sqrt(<h|h>_k)``.  Two
+        ``npf_waveform_loglike_net`` launches; inference only, no host sync, so a ``query`` and its ``loglike_network`` can be
+        captured in one graph (call once at the sizes before capturing) and replayed after ``response`` / ``delays`` were
+        overwritten in place.
+        Out of scope: antenna patterns and delays from a sky position (the caller's, from their GW library); a sky grid per task;
+        gradients; distance marginalisation; sub-grid time interpolation."""
+        if self._y_dim != 2:
+            raise ValueError(f"loglike_network needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_loglike_network_args((rows, T, ld), data, response, delays, weights, freqs, taus)
+        with torch.no_grad():
+            if of == "samples":
+                h = self._suff.detach().reshape(rows, T, ld)
+            else:
+                h = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt)[0]
+            want = tuple(k for k in FN.LOGLIKE_NET_NAMES if k != "tau_index" or taus is not None)
+            m = FN.waveform_loglike_network(h, data, response, delays, weights, freqs, taus, n_valid=self._n_trgt, want=want,
+                                            series=series)
+            lead, D = (rows // B, B), data.shape[1]
+            tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
+            c_abs = torch.hypot(response[..., 0], response[..., 1]).detach()  # [B, D] |C_k|, on the device
+            return NetworkLogLike(m.hh.sqrt().view(lead), m.snr.view(lead), m.lnl_max.view(lead), m.lnl_marg.view(lead),
+                                  m.phase.view(lead), tau, m.tau_index.view(lead) if taus is not None else None, m.lnl_mix,
+                                  m.lnl_max_mix, m.dd, m.series.view(*lead, *m.series.shape[1:]) if series else None,
+                                  m.snr_det.view(*lead, D), m.hh_det.sqrt().view(*lead, D) * c_abs, m.dd_det)
 
     def mismatch(self, Y_ref, weights=None, freqs=None, taus=None, of="samples") -> torch.Tensor:
         """``mismatch`` of :meth:`match` (same arguments, same bits) as a training objective -> [n_z, B], or [1, B] for
