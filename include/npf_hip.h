@@ -28,6 +28,8 @@
  *                        time maximised or marginalised, and marginal over the latent samples (inference; no reference counterpart)
  *   npf_waveform_loglike_net  the coherent likelihood of a detector network: per-detector weights, delays and complex responses,
  *                        the complex correlations added before the modulus (inference; no reference counterpart)
+ *   npf_waveform_loglike_dist/_net_dist  both likelihoods marginalised over a grid of amplitude scales (luminosity distance) as
+ *                        well, with the distance posterior (inference; no reference counterpart)
  *   npf_mc_objective_fwd/bwd  mean / logsumexp / SUMO over the latent samples
  *                                                         npf/losses.py:146,197-200,262-274
  *   npf_mean_agg_fwd/bwd torch.mean(R_cntxt, dim=1)       npf/neuralproc/np.py:95, attnnp.py:181
@@ -840,6 +842,63 @@ int npf_waveform_loglike_net(const float *h, int32_t h_ld, const float *d, const
                              double *dd, double *snr, double *lnl_max, double *lnl_marg, int32_t *tau_index, double *phase,
                              double *series, double *lnl_mix, double *lnl_max_mix, double *hh_det, double *snr_det, double *dd_det,
                              void *workspace, void *stream);
+
+/* ---- distance-marginalised likelihood (csrc/waveform_dist_kernels.hip; no reference counterpart)
+ * The predicted waveform is a template at a reference distance d_ref; at luminosity distance d it is a h with the amplitude scale
+ * a = d_ref / d.  npf_waveform_loglike_dist marginalises the likelihood of npf_waveform_loglike over a grid of scales as well,
+ * npf_waveform_loglike_net_dist that of npf_waveform_loglike_net.  The arguments up to the parent's last output are the parent's; then
+ *   scales[scale_rows][n_a]      DOUBLE, DEVICE data: a_i; scale_rows == 1 (shared by the tasks) or n_tasks
+ *   log_prior[prior_rows][n_a]   DOUBLE, DEVICE data: ln pi_i, the log prior MASS of grid point i (quadrature weight included)
+ * with 1 <= n_a <= NPF_DIST_MAX_SCALES, then the new outputs, then workspace and stream.  The host reads neither tensor: both may be
+ * overwritten in place between the replays of a captured graph.  A scale is LIVE if 0 < a_i < +inf and ln pi_i is finite; nothing else
+ * of a dead scale is used (NaN included).  With x_j, HH (hh of the single stream), j* and the rows r = s * n_tasks + b of the parent,
+ * n = max(n_tau, 1), all in double:
+ *   x*      = x_{j*} = max_j x_j
+ *   M_i     = ln pi_i + (ln I0(a_i x*) - a_i^2 HH / 2)                          (live i)
+ *   S_i     = sum_j exp(ln I0(a_i x_j) - ln I0(a_i x*))                         (every term <= 1: ln I0 increases)
+ *   u_i     = M_i + (ln S_i - ln n)              dead i: u_i = -inf             (the evidence of scale i, phase and time marginalised)
+ *   lnl_dist[r]     = logsumexp_i u_i            (shifted by max_i u_i; no live scale: -inf)
+ *   post[r][i]      = u_i - lnl_dist[r]          (-inf for dead i, and for every i when no scale is live)
+ *   scale_index[r]  = the smallest i that attains max_i u_i   (no live scale: 0)
+ *   scale_hat[r]    = x* / HH        lnl_amp_max[r] = x*^2 / (2 HH)             (both 0 for HH == 0)
+ *   lnl_dist_mix[b] = logsumexp_s lnl_dist[s n_tasks + b] - ln n_z
+ *   post_mix[b][i]  = logsumexp_s u_i[s n_tasks + b] - ln n_z - lnl_dist_mix[b]   (-inf where that is -inf - -inf)
+ * The prior is NOT normalised: lnl_dist carries ln sum_i pi_i as given.  A row with HH == 0 is treated as x_j = 0 for every j:
+ * Lambda = 1 at every scale, lnl_dist = logsumexp_i ln pi_i and post_i = ln pi_i - lnl_dist (the parent's degenerate-row rule,
+ * extended).  With n_a = 1, a = 1, ln pi = 0, u_0 is the expression the parent evaluates for lnl_marg, in its order.  a_i x* and
+ * a_i^2 HH must be finite.  post and post_mix are formed as (u_i - max) - ln sum, the difference first, so that sum_i exp(post_i) = 1
+ * holds to rounding where u reaches 1e6; the mixture keeps its shift and its sum apart for the same reason.
+ * Launches: launch 1 of the parent; the parent's finishing launch only if one of the parent's outputs is requested -- those outputs
+ * come from the parent's kernels and match a plain call bit for bit; then, if one of the new outputs is requested, launch A (one
+ * workgroup per (row, chunk of NPF_DIST_SC scales): x* by the finishing kernels' reduction, x_j kept in LDS up to 4096 grid times and
+ * re-read from the workspace beyond, ln I0(a_i x*) once per scale, S_i strided over j and reduced in a fixed order, u_i into the row's
+ * workspace tail) and launch B (one workgroup per task walks its n_z rows in order; post_mix is a second pass over the u_i).  No
+ * atomics: a second call gives the same bits; the host reads nothing, so the call sits in a captured graph.
+ * New outputs (each may be NULL; with the parent's, at least one must be given; every requested element is written): DOUBLE
+ * lnl_dist / scale_hat / lnl_amp_max [n_rows], int32 scale_index [n_rows], lnl_dist_mix [n_tasks], post [n_rows][n_a],
+ * post_mix [n_tasks][n_a].
+ * workspace: npf_waveform_loglike_dist_workspace_bytes(n_rows, n_det, n_tau, n_a) bytes, 8-byte aligned; n_det == 0: the single
+ * stream.  Per row the parent's doubles, then x* and the n_a values u_i (-1 for sizes the calls refuse).
+ * Status: NPF_EINVAL (nothing launched) for everything the parent refuses but its "no output" rule, n_a outside
+ * [1, NPF_DIST_MAX_SCALES], a NULL scales or log_prior, scale_rows or prior_rows neither 1 nor n_tasks, no output requested at all. */
+#define NPF_DIST_SC 16
+#define NPF_DIST_MAX_SCALES 4096
+int64_t npf_waveform_loglike_dist_workspace_bytes(int32_t n_rows, int32_t n_det, int32_t n_tau, int32_t n_a);
+int npf_waveform_loglike_dist(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                              int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                              double dtau, int32_t n_tau, double *hh, double *dd, double *snr, double *lnl_max, double *lnl_marg,
+                              int32_t *tau_index, double *phase, double *series, double *lnl_mix, double *lnl_max_mix,
+                              const double *scales, int32_t scale_rows, const double *log_prior, int32_t prior_rows, int32_t n_a,
+                              double *lnl_dist, int32_t *scale_index, double *scale_hat, double *lnl_amp_max, double *lnl_dist_mix,
+                              double *post, double *post_mix, void *workspace, void *stream);
+int npf_waveform_loglike_net_dist(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                                  int32_t freq_rows, const int32_t *n_valid, const double *delay, const double *resp, int32_t n_rows,
+                                  int32_t n_tasks, int32_t n_det, int32_t pts, double tau0, double dtau, int32_t n_tau, double *hh,
+                                  double *dd, double *snr, double *lnl_max, double *lnl_marg, int32_t *tau_index, double *phase,
+                                  double *series, double *lnl_mix, double *lnl_max_mix, double *hh_det, double *snr_det, double *dd_det,
+                                  const double *scales, int32_t scale_rows, const double *log_prior, int32_t prior_rows, int32_t n_a,
+                                  double *lnl_dist, int32_t *scale_index, double *scale_hat, double *lnl_amp_max, double *lnl_dist_mix,
+                                  double *post, double *post_mix, void *workspace, void *stream);
 
 int npf_version(void);
 

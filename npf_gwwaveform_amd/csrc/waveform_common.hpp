@@ -1,4 +1,5 @@
-// What waveform_kernels.hip and waveform_net_kernels.hip share: the launch geometry of the correlation launches, the fixed-order
+// What waveform_kernels.hip, waveform_net_kernels.hip and waveform_dist_kernels.hip share: the launch geometry and the workspace rows of
+// the correlation launches, the launch helpers of the two likelihoods, the fixed-order
 // workgroup sum and ln I0 in double.
 #pragma once
 #include "npf_common.hpp"
@@ -11,6 +12,28 @@ constexpr int kWfMaxTau = 65536;
 constexpr double kWfTwoPi = 6.283185307179586476925286766559;
 
 inline int wf_chunks(int n_tau) { return n_tau > 0 ? (n_tau + kWfJC - 1) / kWfJC : 1; }
+
+// doubles per workspace row of the single-stream launches (waveform_kernels.hip) and of the network ones (waveform_net_kernels.hip)
+inline int64_t wf_row_doubles(int n_tau) { return 4 + 2 * (int64_t)kWfJC * wf_chunks(n_tau); }
+inline int64_t wf_net_row_doubles(int n_det, int n_tau) { return 2 + 2 * (int64_t)n_det + 2 * (int64_t)kWfJC * wf_chunks(n_tau); }
+
+// The launches of npf_waveform_loglike / npf_waveform_loglike_net on arguments their entries have checked (wf_loglike_args_bad /
+// wf_loglike_net_args_bad: everything but "no output requested"), over workspace rows of row_doubles doubles -- the layout's own
+// count or more (waveform_dist_kernels.hip keeps a tail behind it).  finish == false: launch 1 only.  -> NPF_OK or NPF_ELAUNCH.
+bool wf_loglike_args_bad(const float* h, int h_ld, const float* d, const float* wgt, int wgt_rows, const float* freq, int freq_rows,
+                         int n_rows, int n_tasks, int pts, int n_tau, const void* workspace);
+int wf_loglike_launch(const float* h, int h_ld, const float* d, const float* wgt, int wgt_rows, const float* freq, int freq_rows,
+                      const int32_t* n_valid, int n_rows, int n_tasks, int pts, double tau0, double dtau, int n_tau, double* hh, double* dd,
+                      double* snr, double* lnl_max, double* lnl_marg, int32_t* tau_index, double* phase, double* series, double* lnl_mix,
+                      double* lnl_max_mix, double* ws, int64_t row_doubles, bool finish, hipStream_t stream);
+bool wf_loglike_net_args_bad(const float* h, int h_ld, const float* d, const float* wgt, int wgt_rows, const float* freq, int freq_rows,
+                             const double* delay, const double* resp, int n_rows, int n_tasks, int n_det, int pts, int n_tau,
+                             const void* workspace);
+int wf_loglike_net_launch(const float* h, int h_ld, const float* d, const float* wgt, int wgt_rows, const float* freq, int freq_rows,
+                          const int32_t* n_valid, const double* delay, const double* resp, int n_rows, int n_tasks, int n_det, int pts,
+                          double tau0, double dtau, int n_tau, double* hh, double* dd, double* snr, double* lnl_max, double* lnl_marg,
+                          int32_t* tau_index, double* phase, double* series, double* lnl_mix, double* lnl_max_mix, double* hh_det,
+                          double* snr_det, double* dd_det, double* ws, int64_t row_doubles, bool finish, hipStream_t stream);
 
 // dst[i] = sum over the workgroup of v[i], i < N (N <= THREADS): lanes by xor shuffles, then the waves in order.  red: N * waves doubles.
 template <int N, int THREADS>

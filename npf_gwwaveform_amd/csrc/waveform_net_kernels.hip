@@ -23,8 +23,6 @@ namespace npf {
 
 constexpr int kWfNetMaxDet = NPF_NET_MAX_DET;
 
-inline int64_t wf_net_row_doubles(int n_det, int n_tau) { return 2 + 2 * (int64_t)n_det + 2 * (int64_t)kWfJC * wf_chunks(n_tau); }
-
 template <int JC, int THREADS>
 __global__ __launch_bounds__(THREADS) void waveform_filter_net_kernel(
     const float* __restrict__ h, int h_ld, const float* __restrict__ d, const float* __restrict__ wgt, int wgt_per_task,
@@ -278,6 +276,39 @@ __global__ __launch_bounds__(kWfLlThreads) void waveform_loglike_net_finish_kern
   }
 }
 
+bool wf_loglike_net_args_bad(const float* h, int h_ld, const float* d, const float* wgt, int wgt_rows, const float* freq, int freq_rows,
+                             const double* delay, const double* resp, int n_rows, int n_tasks, int n_det, int pts, int n_tau,
+                             const void* workspace) {
+  if (!h || !d || !workspace || h_ld < 2 || n_tasks <= 0 || n_rows <= 0 || n_rows > (1 << 24) || n_rows % n_tasks != 0 || pts <= 0)
+    return true;
+  if (n_tau < 0 || n_tau > kWfMaxTau || (n_tau > 0 && !freq)) return true;
+  if (n_det < 1 || n_det > kWfNetMaxDet || !resp || (delay && !freq)) return true;
+  if (wgt && wgt_rows != 1 && wgt_rows != n_tasks) return true;
+  if (freq && freq_rows != 1 && freq_rows != n_tasks) return true;
+  return false;
+}
+
+int wf_loglike_net_launch(const float* h, int h_ld, const float* d, const float* wgt, int wgt_rows, const float* freq, int freq_rows,
+                          const int32_t* n_valid, const double* delay, const double* resp, int n_rows, int n_tasks, int n_det, int pts,
+                          double tau0, double dtau, int n_tau, double* hh, double* dd, double* snr, double* lnl_max, double* lnl_marg,
+                          int32_t* tau_index, double* phase, double* series, double* lnl_mix, double* lnl_max_mix, double* hh_det,
+                          double* snr_det, double* dd_det, double* ws, int64_t row_doubles, bool finish, hipStream_t stream) {
+  if (n_tau == 0) {  // the one candidate is tau = 0; without delays either, freq is not read
+    tau0 = dtau = 0.0;
+    if (!delay) freq = nullptr;
+  }
+  hipLaunchKernelGGL((waveform_filter_net_kernel<kWfJC, kWfThreads>), dim3(n_rows, wf_chunks(n_tau)), dim3(kWfThreads), 0, stream, h, h_ld,
+                     d, wgt, (int)(wgt_rows != 1), freq, (int)(freq_rows != 1), n_valid, delay, resp, n_tasks, n_det, pts, tau0, dtau,
+                     n_tau, ws, row_doubles);
+  NPF_CHECK_LAUNCH();
+  if (!finish) return NPF_OK;
+  hipLaunchKernelGGL(waveform_loglike_net_finish_kernel, dim3(n_tasks), dim3(kWfLlThreads), 0, stream, ws, row_doubles, h, h_ld, d, wgt,
+                     (int)(wgt_rows != 1), freq, (int)(freq_rows != 1), n_valid, delay, n_rows, n_tasks, n_det, pts, tau0, dtau, n_tau, hh,
+                     dd, snr, lnl_max, lnl_marg, tau_index, phase, series, lnl_mix, lnl_max_mix, hh_det, snr_det, dd_det);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}
+
 }  // namespace npf
 
 extern "C" int64_t npf_waveform_loglike_net_workspace_bytes(int32_t n_rows, int32_t n_det, int32_t n_tau) {
@@ -294,29 +325,12 @@ extern "C" int npf_waveform_loglike_net(const float* h, int32_t h_ld, const floa
                                         double* lnl_max_mix, double* hh_det, double* snr_det, double* dd_det, void* workspace,
                                         void* stream) {
   using namespace npf;
-  if (!h || !d || !workspace || h_ld < 2 || n_tasks <= 0 || n_rows <= 0 || n_rows > (1 << 24) || n_rows % n_tasks != 0 || pts <= 0)
+  if (wf_loglike_net_args_bad(h, h_ld, d, wgt, wgt_rows, freq, freq_rows, delay, resp, n_rows, n_tasks, n_det, pts, n_tau, workspace))
     return NPF_EINVAL;
-  if (n_tau < 0 || n_tau > kWfMaxTau || (n_tau > 0 && !freq)) return NPF_EINVAL;
-  if (n_det < 1 || n_det > kWfNetMaxDet || !resp || (delay && !freq)) return NPF_EINVAL;
-  if (wgt && wgt_rows != 1 && wgt_rows != n_tasks) return NPF_EINVAL;
-  if (freq && freq_rows != 1 && freq_rows != n_tasks) return NPF_EINVAL;
   if (!hh && !dd && !snr && !lnl_max && !lnl_marg && !tau_index && !phase && !series && !lnl_mix && !lnl_max_mix && !hh_det &&
       !snr_det && !dd_det)
     return NPF_EINVAL;
-  const int64_t row_doubles = wf_net_row_doubles(n_det, n_tau);
-  double* ws = (double*)workspace;
-  if (n_tau == 0) {  // the one candidate is tau = 0; without delays either, freq is not read
-    tau0 = dtau = 0.0;
-    if (!delay) freq = nullptr;
-  }
-  hipLaunchKernelGGL((waveform_filter_net_kernel<kWfJC, kWfThreads>), dim3(n_rows, wf_chunks(n_tau)), dim3(kWfThreads), 0,
-                     (hipStream_t)stream, h, h_ld, d, wgt, (int)(wgt_rows != 1), freq, (int)(freq_rows != 1), n_valid, delay, resp,
-                     n_tasks, n_det, pts, tau0, dtau, n_tau, ws, row_doubles);
-  NPF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(waveform_loglike_net_finish_kernel, dim3(n_tasks), dim3(kWfLlThreads), 0, (hipStream_t)stream, ws, row_doubles, h,
-                     h_ld, d, wgt, (int)(wgt_rows != 1), freq, (int)(freq_rows != 1), n_valid, delay, n_rows, n_tasks, n_det, pts, tau0,
-                     dtau, n_tau, hh, dd, snr, lnl_max, lnl_marg, tau_index, phase, series, lnl_mix, lnl_max_mix, hh_det, snr_det,
-                     dd_det);
-  NPF_CHECK_LAUNCH();
-  return NPF_OK;
+  return wf_loglike_net_launch(h, h_ld, d, wgt, wgt_rows, freq, freq_rows, n_valid, delay, resp, n_rows, n_tasks, n_det, pts, tau0, dtau,
+                               n_tau, hh, dd, snr, lnl_max, lnl_marg, tau_index, phase, series, lnl_mix, lnl_max_mix, hh_det, snr_det,
+                               dd_det, (double*)workspace, wf_net_row_doubles(n_det, n_tau), true, (hipStream_t)stream);
 }

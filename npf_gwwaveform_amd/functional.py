@@ -677,6 +677,161 @@ def waveform_loglike_network(h: torch.Tensor, data: torch.Tensor, response: torc
     return WaveformLogLikeNetwork(*(out[name] for name in LOGLIKE_NET_NAMES), ser)
 
 
+# ---- distance-marginalised likelihood (csrc/waveform_dist_kernels.hip) --------------
+DIST_SC = 16             # NPF_DIST_SC: scales per workgroup of the scale launch
+DIST_MAX_SCALES = 4096   # NPF_DIST_MAX_SCALES
+LOGLIKE_DIST_NAMES = ("lnl_dist", "scale_index", "scale_hat", "lnl_amp_max", "lnl_dist_mix")
+
+
+class WaveformLogLikeDistance(NamedTuple):
+    """What :func:`waveform_loglike_distance` / :func:`waveform_loglike_network_distance` return (float64 but the two indices); the
+    entries that were not asked for are ``None``."""
+    lnl_dist: Optional[torch.Tensor]      # [R] phase, time and amplitude scale marginalised
+    scale_index: Optional[torch.Tensor]   # [R] int32: the smallest grid index of the largest evidence
+    scale_hat: Optional[torch.Tensor]     # [R] x* / HH: the maximum-likelihood scale (not tied to the grid)
+    lnl_amp_max: Optional[torch.Tensor]   # [R] x*^2 / (2 HH): the amplitude-maximised statistic
+    lnl_dist_mix: Optional[torch.Tensor]  # [B] lnl_dist marginalised over the latent samples
+    post: Optional[torch.Tensor]          # [R, n_a] log posterior mass of every scale
+    post_mix: Optional[torch.Tensor]      # [B, n_a] the same, marginal over the latent samples
+    base: object                          # the WaveformLogLike / WaveformLogLikeNetwork of the same call
+
+
+def check_loglike_distance_args(h_shape, data, scales, log_prior, weights=None, freqs=None, taus=None, response=None, delays=None,
+                                network=False):
+    """The shapes and dtypes of a :func:`waveform_loglike_distance` call (``network=True``: of a
+    :func:`waveform_loglike_network_distance` call) -> ``(geo, scale_rows, prior_rows, n_a)`` with ``geo`` what
+    :func:`check_loglike_args` / :func:`check_loglike_network_args` return; ``ValueError`` for anything that does not fit.  ``scales``
+    and ``log_prior``: float64 tensors [n_a] or [B, n_a] (each on its own), ``1 <= n_a <= DIST_MAX_SCALES``.  Reads no data."""
+    geo = (check_loglike_network_args(h_shape, data, response, delays, weights, freqs, taus) if network
+           else check_loglike_args(h_shape, data, weights, freqs, taus))
+    B = geo[3]
+    n_a = None
+    rows = []
+    for t, what in ((scales, "scales"), (log_prior, "log_prior")):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.dtype != torch.float64:
+            raise ValueError(f"{what} must be a float64 tensor of shape [n_a] or [B={B}, n_a], got "
+                             f"{(list(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.dim() == 2 and t.shape[0] != B:
+            raise ValueError(f"{what} must have shape [n_a] or [B={B}, n_a], got {list(t.shape)}")
+        if not 1 <= t.shape[-1] <= DIST_MAX_SCALES:
+            raise ValueError(f"{what} holds {t.shape[-1]} scales: 1 <= n_a <= {DIST_MAX_SCALES}")
+        if n_a is not None and t.shape[-1] != n_a:
+            raise ValueError(f"scales holds {n_a} grid points, log_prior {t.shape[-1]}")
+        n_a = t.shape[-1]
+        rows.append(1 if t.dim() == 1 else B)
+    return geo, rows[0], rows[1], n_a
+
+
+def _distance_call(network, h, data, response, delays, scales, log_prior, weights, freqs, taus, n_valid, want, posterior):
+    names = LOGLIKE_NET_NAMES if network else LOGLIKE_NAMES
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or any(w not in names + LOGLIKE_DIST_NAMES for w in want):
+        raise ValueError(f"want must be a tuple / list of names out of {names + LOGLIKE_DIST_NAMES}, got {want!r}")
+    want = tuple(want)
+    geo, scale_rows, prior_rows, n_a = check_loglike_distance_args(getattr(h, "shape", ()), data, scales, log_prior, weights, freqs, taus,
+                                                                   response, delays, network)
+    if network:
+        R, T, ld, B, D, wgt_rows, freq_rows, tau0, dtau, n_tau = geo
+    else:
+        (R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau), D = geo, 0
+    if not want and not posterior:
+        raise ValueError(f"want must name at least one of {names + LOGLIKE_DIST_NAMES} (or posterior=True)")
+    for t in (h, data, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    for t, what in ((response, "response"), (delays, "delays"), (scales, "scales"), (log_prior, "log_prior")):
+        if t is not None and (not t.is_cuda or t.device != h.device):
+            raise ValueError(f"{what} must live on the device of h ({h.device}), got {t.device}: the kernel reads it there")
+    h, data = h.detach().contiguous(), data.detach().contiguous()
+    scales, log_prior = scales.detach().contiguous(), log_prior.detach().contiguous()
+    response = response.detach().contiguous() if response is not None else None
+    delays = delays.detach().contiguous() if delays is not None else None
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and (n_tau > 0 or delays is not None) else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    lib = L.load()
+    ws = _match_workspace(h.device, int(lib.npf_waveform_loglike_dist_workspace_bytes(R, D, n_tau, n_a)))
+
+    def new(name):
+        rows = B if name in _LOGLIKE_PER_TASK or name in ("dd_det", "lnl_dist_mix") else R
+        return torch.empty((rows, D) if name in _LOGLIKE_NET_PER_DET else (rows,),
+                           dtype=torch.int32 if name in ("tau_index", "scale_index") else torch.float64, device=h.device)
+
+    out = {name: (new(name) if name in want else None) for name in names + LOGLIKE_DIST_NAMES}
+    post = torch.empty((R, n_a), dtype=torch.float64, device=h.device) if posterior else None
+    post_mix = torch.empty((B, n_a), dtype=torch.float64, device=h.device) if posterior else None
+    dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    parent = [dptr(out[name]) for name in ("hh", "dd", "snr", "lnl_max", "lnl_marg", "tau_index", "phase")] + \
+        [None, dptr(out["lnl_mix"]), dptr(out["lnl_max_mix"])]  # (no series: ``post`` is this call's grid output)
+    tail = (dptr(scales), scale_rows, dptr(log_prior), prior_rows, n_a, *(dptr(out[name]) for name in LOGLIKE_DIST_NAMES), dptr(post),
+            dptr(post_mix), ws.data_ptr(), L.stream_ptr())
+    head = (L.ptr(h), ld, L.ptr(data), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows, _iptr(nv) if nv is not None else None)
+    if network:
+        L.check(lib.npf_waveform_loglike_net_dist(*head, dptr(delays), dptr(response), R, B, D, T, tau0, dtau, n_tau, *parent,
+                                                  dptr(out["hh_det"]), dptr(out["snr_det"]), dptr(out["dd_det"]), *tail),
+                "npf_waveform_loglike_net_dist")
+        base = WaveformLogLikeNetwork(*(out[name] for name in LOGLIKE_NET_NAMES), None)
+    else:
+        L.check(lib.npf_waveform_loglike_dist(*head, R, B, T, tau0, dtau, n_tau, *parent, *tail), "npf_waveform_loglike_dist")
+        base = WaveformLogLike(*(out[name] for name in LOGLIKE_NAMES), None)
+    return WaveformLogLikeDistance(*(out[name] for name in LOGLIKE_DIST_NAMES), post, post_mix, base)
+
+
+def waveform_loglike_distance(h: torch.Tensor, data: torch.Tensor, scales: torch.Tensor, log_prior: torch.Tensor,
+                              weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None, taus=None,
+                              n_valid: Optional[torch.Tensor] = None, want=LOGLIKE_NAMES + LOGLIKE_DIST_NAMES,
+                              posterior: bool = False) -> WaveformLogLikeDistance:
+    """The likelihood of :func:`waveform_loglike` marginalised over the amplitude scale of the template as well -- for a template
+    ``h`` at a reference distance ``d_ref``, over the luminosity distance ``d = d_ref / a``.  ``scales`` (``a_i``) and ``log_prior``
+    (``ln pi_i``, the log prior MASS of grid point ``i``, quadrature weight included; :func:`distance_prior` makes both from
+    distances) are float64 DEVICE tensors [n_a] or [B, n_a], ``1 <= n_a <= DIST_MAX_SCALES``, taken as they are: the host reads
+    neither, so a captured graph sees what they hold at replay.  A scale is live if ``0 < a_i < inf`` and ``ln pi_i`` is finite;
+    nothing else of a dead scale is used.  With ``x_j = |kappa_j|``, ``x* = max_j x_j``, ``n = max(n_tau, 1)``:
+    ``u_i = ln pi_i + ln I0(a_i x*) - a_i^2 hh / 2 + ln sum_j exp(ln I0(a_i x_j) - ln I0(a_i x*)) - ln n`` (``-inf`` for a dead scale)
+    is the evidence of scale ``i``, marginal over phase and grid time; ``lnl_dist = logsumexp_i u_i`` (no live scale: ``-inf``),
+    ``scale_index`` the smallest index of ``max_i u_i`` (no live scale: 0), ``scale_hat = x* / hh`` and ``lnl_amp_max = x*^2 / (2
+    hh)`` the maximum-likelihood scale and statistic (0 for ``hh == 0``), ``lnl_dist_mix`` [B] the log-mean-exp of ``lnl_dist`` over
+    the latent samples.  ``posterior=True`` adds ``post`` [R, n_a] ``= u_i - lnl_dist`` and ``post_mix`` [B, n_a], the log posterior
+    mass of every scale per latent sample and marginal over them (``-inf`` at dead scales, everywhere when no scale is live).  The
+    prior is not normalised by the kernel.  A row with ``hh == 0`` has ``Lambda = 1`` at every scale: ``post_i = ln pi_i -
+    logsumexp ln pi``.  ``want``: names out of ``LOGLIKE_NAMES + LOGLIKE_DIST_NAMES``; the parent's come back in ``base``, from the
+    parent's own kernels, bit-equal to a plain :func:`waveform_loglike` call (its finishing launch runs only if one is asked for).
+    Launch 1 of the parent, then two ``npf_waveform_loglike_dist`` launches; double arithmetic, inference only, no host sync,
+    deterministic; the workspace is the one of :func:`waveform_match`.  ``include/npf_hip.h`` has the contract."""
+    return _distance_call(False, h, data, None, None, scales, log_prior, weights, freqs, taus, n_valid, want, posterior)
+
+
+def waveform_loglike_network_distance(h: torch.Tensor, data: torch.Tensor, response: torch.Tensor, delays: Optional[torch.Tensor],
+                                      scales: torch.Tensor, log_prior: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                                      freqs: Optional[torch.Tensor] = None, taus=None, n_valid: Optional[torch.Tensor] = None,
+                                      want=LOGLIKE_NET_NAMES + LOGLIKE_DIST_NAMES, posterior: bool = False) -> WaveformLogLikeDistance:
+    """:func:`waveform_loglike_distance` over the network sums of :func:`waveform_loglike_network` (``K_j``, ``HH`` in place of
+    ``kappa_j``, ``hh``): one amplitude scale, one phase and one arrival time are shared by the detectors.  ``data``, ``response``,
+    ``delays`` (``None``: zeros), ``weights``, ``freqs``, ``taus``, ``n_valid``: as in :func:`waveform_loglike_network`; ``scales``,
+    ``log_prior``, ``posterior`` and the results: as in :func:`waveform_loglike_distance`; ``want``: names out of
+    ``LOGLIKE_NET_NAMES + LOGLIKE_DIST_NAMES``."""
+    return _distance_call(True, h, data, response, delays, scales, log_prior, weights, freqs, taus, n_valid, want, posterior)
+
+
+def distance_prior(distances: torch.Tensor, d_ref: float, power: float = 2.0):
+    """``(scales, log_prior)`` of :func:`waveform_loglike_distance` from a grid of luminosity distances: ``distances`` float64 [n_a]
+    or [B, n_a], positive and increasing along the last axis (the units of ``d_ref``, the distance the template is predicted at).
+    ``scales = d_ref / distances``; ``log_prior = ln(d^power x trapezoid width)`` -- the width of point ``i`` is half the distance
+    between its neighbours, half the one interval at either end, 1 for a single point -- normalised to total mass 1 per row.
+    ``power = 2``: uniform in volume.  Plain torch on the device of ``distances``; no host read."""
+    if not isinstance(distances, torch.Tensor) or distances.dim() not in (1, 2) or distances.dtype != torch.float64 or \
+            distances.shape[-1] < 1:
+        raise ValueError("distances must be a float64 tensor of shape [n_a] or [B, n_a], got "
+                         f"{(list(distances.shape), distances.dtype) if isinstance(distances, torch.Tensor) else type(distances).__name__}")
+    d = distances.detach()
+    if d.shape[-1] == 1:
+        width = torch.ones_like(d)
+    else:
+        gap = d[..., 1:] - d[..., :-1]
+        width = 0.5 * (torch.nn.functional.pad(gap, (1, 0)) + torch.nn.functional.pad(gap, (0, 1)))
+    lp = float(power) * torch.log(d) + torch.log(width)
+    return float(d_ref) / d, lp - torch.logsumexp(lp, -1, keepdim=True)
+
+
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------
 MC_MEAN, MC_LOGMEANEXP, MC_SUMO = 0, 1, 2
 

@@ -31,7 +31,8 @@ from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlat
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "LogLike", "NetworkLogLike", "Reweighted", "bootstrap_weights",
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "LogLike", "NetworkLogLike", "DistanceLogLike",
+           "NetworkDistanceLogLike", "Reweighted", "bootstrap_weights",
            "kfold_weights"]
 
 
@@ -106,6 +107,53 @@ class NetworkLogLike(NamedTuple):
     snr_det: torch.Tensor              # [.., B, D] |<d_k|h>_k| / sqrt(<h|h>_k) at the network's grid time
     optimal_snr_det: torch.Tensor      # [.., B, D] |C_k| sqrt(<h|h>_k)
     dd_det: torch.Tensor               # [B, D] <d_k|d_k>
+
+
+class DistanceLogLike(NamedTuple):
+    """Distance-marginalised likelihood (:meth:`HeadDistribution.loglike_distance`), float64 (but the indices).  Per (latent sample,
+    task): [n_z, B] for ``of="samples"``, [1, B] for ``of="mean"``; per task: [B]; per scale: a last axis of ``n_a``."""
+    lnl: torch.Tensor                  # [B] lnl_dist marginalised over the latent samples: log-mean-exp
+    lnl_dist: torch.Tensor             # ln Lambda marginalised over phase, grid times and the amplitude scale (prior mass as given)
+    scale_hat: torch.Tensor            # <d|h> / <h|h> at the maximum: the maximum-likelihood scale; distance d_ref / scale_hat
+    lnl_amp_max: torch.Tensor          # snr^2 / 2: ln Lambda maximised over phase, grid times and amplitude
+    scale_index: torch.Tensor          # int32: the grid scale of the largest evidence, the smallest index
+    scale_map: torch.Tensor            # ``scales`` gathered there
+    post: Optional[torch.Tensor]       # [.., B, n_a] log posterior mass of every scale (``posterior=True``)
+    post_mix: Optional[torch.Tensor]   # [B, n_a] the same with the latent samples marginalised (``posterior=True``)
+    base: LogLike                      # :meth:`HeadDistribution.loglike` of the same call (no series)
+
+
+class NetworkDistanceLogLike(NamedTuple):
+    """:class:`DistanceLogLike` over the network sums (:meth:`HeadDistribution.loglike_network_distance`); ``base`` is the
+    :class:`NetworkLogLike` of the same call."""
+    lnl: torch.Tensor
+    lnl_dist: torch.Tensor
+    scale_hat: torch.Tensor
+    lnl_amp_max: torch.Tensor
+    scale_index: torch.Tensor
+    scale_map: torch.Tensor
+    post: Optional[torch.Tensor]
+    post_mix: Optional[torch.Tensor]
+    base: NetworkLogLike
+
+
+def _as_loglike(m, taus, lead) -> LogLike:
+    """A ``functional.WaveformLogLike`` (every name but ``tau_index`` without ``taus``) with its per-row entries shaped ``lead``."""
+    tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
+    return LogLike(m.hh.sqrt().view(lead), m.snr.view(lead), m.lnl_max.view(lead), m.lnl_marg.view(lead), m.phase.view(lead),
+                   tau, m.tau_index.view(lead) if taus is not None else None, m.lnl_mix, m.lnl_max_mix, m.dd,
+                   m.series.view(*lead, *m.series.shape[1:]) if m.series is not None else None)
+
+
+def _as_network_loglike(m, taus, lead, response) -> NetworkLogLike:
+    """The same of a ``functional.WaveformLogLikeNetwork``."""
+    D = response.shape[1]
+    tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
+    c_abs = torch.hypot(response[..., 0], response[..., 1]).detach()  # [B, D] |C_k|, on the device
+    return NetworkLogLike(m.hh.sqrt().view(lead), m.snr.view(lead), m.lnl_max.view(lead), m.lnl_marg.view(lead),
+                          m.phase.view(lead), tau, m.tau_index.view(lead) if taus is not None else None, m.lnl_mix,
+                          m.lnl_max_mix, m.dd, m.series.view(*lead, *m.series.shape[1:]) if m.series is not None else None,
+                          m.snr_det.view(*lead, D), m.hh_det.sqrt().view(*lead, D) * c_abs, m.dd_det)
 
 
 class HeadDistribution(Independent):
@@ -219,9 +267,9 @@ class HeadDistribution(Independent):
         deterministic model.  Padded targets (``n_trgt``) are left out.  ``series=True`` adds ``(L_j, SNR_j)`` over the grid.
         Two ``npf_waveform_loglike`` launches; inference only, no host sync, so a ``query`` and its ``loglike`` can be captured in
         one graph (call once at the sizes before capturing: the workspace is allocated then).
+        Distance / amplitude marginalisation is :meth:`loglike_distance`, which returns this result as its ``base``.
         Out of scope: gradients of the likelihood; marginalising the head's per-point sigma (only the latent samples are
-        marginalised); distance / amplitude marginalisation (the amplitude-maximised statistic is ``snr ** 2 / 2``, which the
-        caller forms); non-uniform time priors; sub-grid time interpolation."""
+        marginalised); non-uniform time priors; sub-grid time interpolation."""
         if self._y_dim != 2:
             raise ValueError(f"loglike needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
         if of not in ("samples", "mean"):
@@ -236,11 +284,7 @@ class HeadDistribution(Independent):
                 h = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt)[0]
             want = tuple(k for k in FN.LOGLIKE_NAMES if k != "tau_index" or taus is not None)
             m = FN.waveform_loglike(h, data, weights, freqs, taus, n_valid=self._n_trgt, want=want, series=series)
-            lead = (rows // B, B)
-            tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
-            return LogLike(m.hh.sqrt().view(lead), m.snr.view(lead), m.lnl_max.view(lead), m.lnl_marg.view(lead), m.phase.view(lead),
-                           tau, m.tau_index.view(lead) if taus is not None else None, m.lnl_mix, m.lnl_max_mix, m.dd,
-                           m.series.view(*lead, *m.series.shape[1:]) if series else None)
+            return _as_loglike(m, taus, (rows // B, B))
 
     def loglike_network(self, data, response, delays=None, weights=None, freqs=None, taus=None, of="samples",
                         series=False) -> NetworkLogLike:
@@ -257,9 +301,9 @@ class HeadDistribution(Independent):
         each detector's own SNR at the network's grid time, ``optimal_snr_det = |C_k| sqrt(<h|h>_k)``.  Two
         ``npf_waveform_loglike_net`` launches; inference only, no host sync, so a ``query`` and its ``loglike_network`` can be
         captured in one graph (call once at the sizes before capturing) and replayed after ``response`` / ``delays`` were
-        overwritten in place.
+        overwritten in place.  The distance marginalisation of this likelihood is :meth:`loglike_network_distance`.
         Out of scope: antenna patterns and delays from a sky position (the caller's, from their GW library); a sky grid per task;
-        gradients; distance marginalisation; sub-grid time interpolation."""
+        gradients; sub-grid time interpolation."""
         if self._y_dim != 2:
             raise ValueError(f"loglike_network needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
         if of not in ("samples", "mean"):
@@ -275,13 +319,86 @@ class HeadDistribution(Independent):
             want = tuple(k for k in FN.LOGLIKE_NET_NAMES if k != "tau_index" or taus is not None)
             m = FN.waveform_loglike_network(h, data, response, delays, weights, freqs, taus, n_valid=self._n_trgt, want=want,
                                             series=series)
-            lead, D = (rows // B, B), data.shape[1]
-            tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
-            c_abs = torch.hypot(response[..., 0], response[..., 1]).detach()  # [B, D] |C_k|, on the device
-            return NetworkLogLike(m.hh.sqrt().view(lead), m.snr.view(lead), m.lnl_max.view(lead), m.lnl_marg.view(lead),
-                                  m.phase.view(lead), tau, m.tau_index.view(lead) if taus is not None else None, m.lnl_mix,
-                                  m.lnl_max_mix, m.dd, m.series.view(*lead, *m.series.shape[1:]) if series else None,
-                                  m.snr_det.view(*lead, D), m.hh_det.sqrt().view(*lead, D) * c_abs, m.dd_det)
+            return _as_network_loglike(m, taus, (rows // B, B), response)
+
+    def loglike_distance(self, data, scales, log_prior, weights=None, freqs=None, taus=None, of="samples",
+                         posterior=False) -> DistanceLogLike:
+        """:meth:`loglike` marginalised over the luminosity distance as well -> :class:`DistanceLogLike`.  The predicted waveform is
+        the template at a reference distance ``d_ref``; at distance ``d`` it is ``a h`` with the amplitude scale ``a = d_ref / d``.
+        ``scales`` (``a_i``) and ``log_prior`` (``ln pi_i``: the log prior MASS of grid point ``i``, quadrature weight included) are
+        float64 device tensors [n_a] or [B, n_a] the host never reads (``functional.distance_prior`` makes both from a grid of
+        distances).  A scale with ``a_i`` outside (0, inf) or a ``ln pi_i`` that is not finite is dead: it gets no mass and nothing
+        else of it is used.  ``lnl_dist`` is the likelihood marginal over the coalescence phase, the grid of arrival times and the
+        scale grid (the prior is not normalised: ``lnl_dist`` carries ``ln sum_i pi_i`` as given), ``lnl`` [B] its log-mean-exp over
+        the latent samples; ``scale_hat = <d|h> / <h|h>`` at the maximum gives the maximum-likelihood distance ``d_ref /
+        scale_hat`` and ``lnl_amp_max = snr ** 2 / 2`` the amplitude-maximised statistic; ``scale_index`` / ``scale_map`` are the
+        grid point of the largest evidence.  ``posterior=True`` adds the log posterior mass of every scale: ``post`` per latent
+        sample and ``post_mix`` [B, n_a] with the model's own waveform uncertainty marginalised out -- the distance posterior.
+        Where no scale is live ``lnl_dist`` and every ``post`` are ``-inf`` and ``scale_index`` is 0; a task without live points or
+        with a zero template has ``Lambda = 1`` at every scale, so its posterior is the normalised prior.  ``base`` is the
+        :class:`LogLike` of :meth:`loglike` on the same inputs, bit for bit.  ``weights``, ``freqs``, ``taus``, ``of``, padded
+        targets: as in :meth:`loglike`.  One correlation launch, the finishing launch of :meth:`loglike` and two
+        ``npf_waveform_loglike_dist`` launches; inference only, no host sync, so a ``query`` and its ``loglike_distance`` can be
+        captured in one graph (call once at the sizes before capturing) and replayed after ``scales`` / ``log_prior`` were
+        overwritten in place.
+        Out of scope: gradients; non-uniform time priors; marginalising the head's per-point sigma; continuous (non-grid) amplitude
+        integration."""
+        if self._y_dim != 2:
+            raise ValueError(f"loglike_distance needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_loglike_distance_args((rows, T, ld), data, scales, log_prior, weights, freqs, taus)
+        with torch.no_grad():
+            h = self._waveform_rows(of, rows, ld)
+            want = tuple(k for k in FN.LOGLIKE_NAMES if k != "tau_index" or taus is not None) + FN.LOGLIKE_DIST_NAMES
+            m = FN.waveform_loglike_distance(h, data, scales, log_prior, weights, freqs, taus, n_valid=self._n_trgt, want=want,
+                                             posterior=posterior)
+            lead = (rows // B, B)
+            return DistanceLogLike(*self._distance_fields(m, scales, lead), _as_loglike(m.base, taus, lead))
+
+    def loglike_network_distance(self, data, response, delays, scales, log_prior, weights=None, freqs=None, taus=None, of="samples",
+                                 posterior=False) -> NetworkDistanceLogLike:
+        """:meth:`loglike_network` marginalised over the luminosity distance as well -> :class:`NetworkDistanceLogLike`: what
+        :meth:`loglike_distance` computes, over the network sums -- one amplitude scale, one coalescence phase and one geocentric
+        arrival time are shared by the detectors.  ``data``, ``response``, ``delays`` (``None``: zeros), ``weights``, ``freqs``,
+        ``taus``, ``of``: as in :meth:`loglike_network`; ``scales``, ``log_prior``, ``posterior`` and the fields: as in
+        :meth:`loglike_distance`; ``base`` is the :class:`NetworkLogLike` of :meth:`loglike_network` on the same inputs, bit for
+        bit.  Inference only, no host sync; ``response``, ``delays``, ``scales`` and ``log_prior`` may be overwritten in place
+        between the replays of a captured graph."""
+        if self._y_dim != 2:
+            raise ValueError("loglike_network_distance needs a model whose two outputs are (amplitude, phase): y_dim == 2, got "
+                             f"{self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_loglike_distance_args((rows, T, ld), data, scales, log_prior, weights, freqs, taus, response, delays, network=True)
+        with torch.no_grad():
+            h = self._waveform_rows(of, rows, ld)
+            want = tuple(k for k in FN.LOGLIKE_NET_NAMES if k != "tau_index" or taus is not None) + FN.LOGLIKE_DIST_NAMES
+            m = FN.waveform_loglike_network_distance(h, data, response, delays, scales, log_prior, weights, freqs, taus,
+                                                     n_valid=self._n_trgt, want=want, posterior=posterior)
+            lead = (rows // B, B)
+            return NetworkDistanceLogLike(*self._distance_fields(m, scales, lead), _as_network_loglike(m.base, taus, lead, response))
+
+    def _waveform_rows(self, of, rows, ld):
+        """The (amplitude, phase) rows a likelihood is evaluated on: the raw decoder output or the mixture mean."""
+        n_z, _, T = self.batch_shape
+        if of == "samples":
+            return self._suff.detach().reshape(rows, T, ld)
+        return FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt)[0]
+
+    @staticmethod
+    def _distance_fields(m, scales, lead):
+        """The fields of :class:`DistanceLogLike` before ``base``, from a ``functional.WaveformLogLikeDistance``."""
+        idx = m.scale_index.view(lead).long()
+        grid = scales.detach()
+        scale_map = grid[idx] if grid.dim() == 1 else grid.gather(1, idx.t()).t()  # ([B, n_a]: task b's own grid)
+        n_a = scales.shape[-1]
+        return (m.lnl_dist_mix, m.lnl_dist.view(lead), m.scale_hat.view(lead), m.lnl_amp_max.view(lead), m.scale_index.view(lead),
+                scale_map, m.post.view(*lead, n_a) if m.post is not None else None, m.post_mix)
 
     def mismatch(self, Y_ref, weights=None, freqs=None, taus=None, of="samples") -> torch.Tensor:
         """``mismatch`` of :meth:`match` (same arguments, same bits) as a training objective -> [n_z, B], or [1, B] for
