@@ -900,6 +900,69 @@ int npf_waveform_loglike_net_dist(const float *h, int32_t h_ld, const float *d, 
                                   double *lnl_dist, int32_t *scale_index, double *scale_hat, double *lnl_amp_max, double *lnl_dist_mix,
                                   double *post, double *post_mix, void *workspace, void *stream);
 
+/* ---- gradient of the matched-filter likelihoods with respect to the predicted waveform (csrc/waveform_grad_kernels.hip; no reference
+ * counterpart).  npf_waveform_loglike_ex / npf_waveform_loglike_net_ex are npf_waveform_loglike / npf_waveform_loglike_net with one
+ * more argument before workspace: every output of the parent comes from the parent's own launches and is BIT-EQUAL to a plain call,
+ * and a third launch (one workgroup per row over the workspace row launch 1 left, the maximum and the shifted sum in the finishing
+ * launch's order) fills
+ *   saved[n_rows][npf_waveform_loglike_saved_doubles(n_tau) = 4 + 2 n]   DOUBLE, n = max(n_tau, 1), the caller's (the workspace may be
+ *     reused before the backward runs): [hh (the network: HH), Re conj(u_{j*}), Im conj(u_{j*}), 0, (Re q_j, Im q_j) j < n]
+ * with x_j = |kappa_j| (|K_j|), u_j = kappa_j / x_j (0 where x_j == 0), p_j = exp(L_j - logsumexp_j L_j), rho = I1 / I0 and
+ *   q_j = p_j rho(x_j) conj(u_j)                                  (|sum_j q_j| <= 1; a row with hh == 0: all zeros)
+ * rho(x) in double: below NPF_LOGLIKE_I0_SWITCH (x / 2) S1 / S0 with the power series S0 = sum_k (x^2 / 4)^k / (k!)^2 and
+ * S1 = sum_k (x^2 / 4)^k / (k! (k + 1)!); from there on the ratio of the two 16-term series in 1 / (8 x).  rho(0) = 0, no overflow.
+ * The parent's "no output" rule does not apply (saved is one); a NULL saved is NPF_EINVAL.
+ *
+ * npf_waveform_loglike_bwd / npf_waveform_loglike_net_bwd: the gradient of a scalar F of the four likelihoods with respect to (A, phi).
+ * Upstream gradients, DOUBLE, DEVICE data, each may be NULL (at least one must be given): d_marg / d_max [n_rows] of lnl_marg /
+ * lnl_max, d_mix / d_max_mix [n_tasks] of lnl_mix / lnl_max_mix; lnl_marg, lnl_max, lnl_mix, lnl_max_mix: what the forward returned
+ * (read only for a mixture's gradient, which needs both of its tensors).  Per row, with b = r % n_tasks, n_z = n_rows / n_tasks,
+ *   g_marg = d_marg[r] + d_mix[b] exp(lnl_marg[r] - lnl_mix[b]) / n_z        g_max likewise from d_max, d_max_mix
+ *   G_t    = g_marg sum_j q_j e^{i 2 pi f_t tau_j} + g_max conj(u_{j*}) e^{i 2 pi f_t tau_{j*}}     (n_tau == 0: no time factors)
+ *   E_t    = conj(d_t) e^{i phi_t}
+ *   dF/dA_t = w_t (Re(E_t G_t) - (g_marg + g_max) A_t)          dF/dphi_t = -w_t A_t Im(E_t G_t)
+ * and for the network, over the detectors that are live at t in ascending k, with the one G_t:
+ *   E_{k,t} = C_k conj(d_{k,t}) e^{i (phi_t + 2 pi f_t delay_k)}
+ *   dA += w_{k,t} (Re(E_{k,t} G_t) - (g_marg + g_max) |C_k|^2 A_t)          dphi -= w_{k,t} A_t Im(E_{k,t} G_t)
+ * The lnl_marg term is exact; the lnl_max term is the derivative at j* = tau_index[r], the grid time the forward found (at a tie the
+ * smallest index: a subgradient, as in npf_waveform_match_bwd).  d_h, n_bcast, dh_ld: as in npf_waveform_match_bwd -- row
+ * q * n_rows + r receives 1 / n_bcast of row r's gradient, entries 2 .. dh_ld - 1 get exact zeros, EVERY element is written.  A point
+ * that is not live (the network: for any detector), a point at or beyond n_valid[b] and every point of a row with hh == 0 get exact
+ * zeros, SELECTED: nothing of such a point is read, nor the upstream gradients of such a row, and a NaN there cannot reach d_h.
+ * (For hh == 0 the zero is the limit of the marginal's gradient: rho(0) = 0.)  No gradient with respect to d, wgt, freq, resp, delay.
+ * One launch: grid (n_rows, min(ceil(pts / 256), 1024)), one thread per point with a grid-stride loop; the workgroup stages 256
+ * shifts of the row's coefficients in LDS at a time; per point and chunk of NPF_WAVEFORM_JC shifts one double sincos of
+ * 2 pi f_t tau_{j0}, one of 2 pi f_t dtau per point, then G += q_j z, z <- z s; one sincos of phi_t per point, for the network one
+ * per (point, live detector) where delay is given.  Everything in double, one rounding to fp32 per output; no reduction across
+ * threads, no atomics: the same inputs give the same bits.  The host reads nothing: the call sits in a captured graph.
+ * Status: NPF_EINVAL (nothing launched) for the sizes the forward refuses, a NULL h, d, saved or d_h, n_tau > 0 with freq or
+ * tau_index NULL, no upstream gradient, d_mix without lnl_marg and lnl_mix, d_max_mix without lnl_max and lnl_max_mix, n_bcast < 1,
+ * dh_ld < 2; the network: n_det outside [1, NPF_NET_MAX_DET], a NULL resp, delay given with a NULL freq. */
+int64_t npf_waveform_loglike_saved_doubles(int32_t n_tau);
+int npf_waveform_loglike_ex(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                            int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                            double dtau, int32_t n_tau, double *hh, double *dd, double *snr, double *lnl_max, double *lnl_marg,
+                            int32_t *tau_index, double *phase, double *series, double *lnl_mix, double *lnl_max_mix, double *saved,
+                            void *workspace, void *stream);
+int npf_waveform_loglike_net_ex(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                                int32_t freq_rows, const int32_t *n_valid, const double *delay, const double *resp, int32_t n_rows,
+                                int32_t n_tasks, int32_t n_det, int32_t pts, double tau0, double dtau, int32_t n_tau, double *hh,
+                                double *dd, double *snr, double *lnl_max, double *lnl_marg, int32_t *tau_index, double *phase,
+                                double *series, double *lnl_mix, double *lnl_max_mix, double *hh_det, double *snr_det, double *dd_det,
+                                double *saved, void *workspace, void *stream);
+int npf_waveform_loglike_bwd(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                             int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
+                             double dtau, int32_t n_tau, const int32_t *tau_index, const double *saved, const double *lnl_marg,
+                             const double *lnl_max, const double *lnl_mix, const double *lnl_max_mix, const double *d_marg,
+                             const double *d_max, const double *d_mix, const double *d_max_mix, int32_t n_bcast, float *d_h,
+                             int32_t dh_ld, void *stream);
+int npf_waveform_loglike_net_bwd(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                                 int32_t freq_rows, const int32_t *n_valid, const double *delay, const double *resp, int32_t n_rows,
+                                 int32_t n_tasks, int32_t n_det, int32_t pts, double tau0, double dtau, int32_t n_tau,
+                                 const int32_t *tau_index, const double *saved, const double *lnl_marg, const double *lnl_max,
+                                 const double *lnl_mix, const double *lnl_max_mix, const double *d_marg, const double *d_max,
+                                 const double *d_mix, const double *d_max_mix, int32_t n_bcast, float *d_h, int32_t dh_ld, void *stream);
+
 int npf_version(void);
 
 #ifdef __cplusplus

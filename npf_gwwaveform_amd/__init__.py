@@ -9,8 +9,8 @@ from .architectures import (MLP, DotAttender, KeyWeights, MergeFlatInputs, Multi
 from .chain import set_compute_dtype
 from .datasplit import CntxtTrgtGetter, GetRandomIndcs, GetRangeIndcs, get_all_indcs
 from .evaluate import eval_loglike
-from .losses import CNPFLoss, ELBOLossLNPF, LightTailPareto, MismatchLoss, NLLLossLNPF, SUMOLossLNPF
-from .neuralproc import (CNP, LNP, AttnCNP, AttnLNP, Conditioned, DistanceLogLike, HeadDistribution, LatentNeuralProcessFamily, LogLike, Match,
+from .losses import CNPFLoss, ELBOLossLNPF, LightTailPareto, LogLikeLoss, MismatchLoss, NLLLossLNPF, SUMOLossLNPF
+from .neuralproc import (CNP, LNP, AttnCNP, AttnLNP, Conditioned, DistanceLogLike, HeadDistribution, LatentNeuralProcessFamily, Lnl, LogLike, Match,
                          MultivariateNormalDiag, NetworkDistanceLogLike, NetworkLogLike, NeuralProcessFamily, Prediction, Reweighted, Score, bootstrap_weights, kfold_weights)
 
 # north-star aliases: NPFModel / encode / aggregate / decode
@@ -37,7 +37,7 @@ def decode(model: NeuralProcessFamily, X_trgt_enc, R_trgt):
 __all__ = [
     "MLP", "MergeFlatInputs", "merge_flat_input", "DotAttender", "MultiheadAttender", "TransformerAttender", "SelfAttention", "get_attender",
     "NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP", "NPFModel",
-    "CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LightTailPareto", "MultivariateNormalDiag", "encode", "aggregate", "decode",
+    "CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LogLikeLoss", "LightTailPareto", "MultivariateNormalDiag", "encode", "aggregate", "decode",
     "CntxtTrgtGetter", "GetRandomIndcs", "GetRangeIndcs", "get_all_indcs", "set_compute_dtype", "eval_loglike", "HeadDistribution",
-    "Conditioned", "Prediction", "Score", "Match", "LogLike", "NetworkLogLike", "DistanceLogLike", "NetworkDistanceLogLike", "Reweighted", "KeyWeights", "TrainKeyWeights", "bootstrap_weights", "kfold_weights",
+    "Conditioned", "Prediction", "Score", "Match", "LogLike", "Lnl", "NetworkLogLike", "DistanceLogLike", "NetworkDistanceLogLike", "Reweighted", "KeyWeights", "TrainKeyWeights", "bootstrap_weights", "kfold_weights",
 ]

@@ -169,6 +169,15 @@ SIGNATURES = {
     "npf_waveform_loglike_net_dist": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_double,
                                                 C.c_double, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32,
                                                 _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "npf_waveform_loglike_saved_doubles": (_i64, [_i32]),
+    "npf_waveform_loglike_ex": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
+                                          _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "npf_waveform_loglike_net_ex": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_double,
+                                              C.c_double, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "npf_waveform_loglike_bwd": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
+                                           _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _p]),
+    "npf_waveform_loglike_net_bwd": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_double,
+                                               C.c_double, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32, _p]),
     "npf_version": (C.c_int, []),
 }
 

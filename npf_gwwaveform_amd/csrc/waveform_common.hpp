@@ -1,6 +1,6 @@
-// What waveform_kernels.hip, waveform_net_kernels.hip and waveform_dist_kernels.hip share: the launch geometry and the workspace rows of
-// the correlation launches, the launch helpers of the two likelihoods, the fixed-order
-// workgroup sum and ln I0 in double.
+// What waveform_kernels.hip, waveform_net_kernels.hip, waveform_dist_kernels.hip and waveform_grad_kernels.hip share: the launch
+// geometry and the workspace rows of the correlation launches, the launch helpers of the two likelihoods, the fixed-order
+// workgroup sum, ln I0 and I1 / I0 in double.
 #pragma once
 #include "npf_common.hpp"
 
@@ -8,6 +8,8 @@ namespace npf {
 
 constexpr int kWfJC = NPF_WAVEFORM_JC;  // time shifts per workgroup of launch 1
 constexpr int kWfThreads = 128;
+constexpr int kWfBwdThreads = 256;  // points per workgroup pass of the backward launches
+constexpr int kWfBwdMaxGridY = 1024;
 constexpr int kWfMaxTau = 65536;
 constexpr double kWfTwoPi = 6.283185307179586476925286766559;
 
@@ -85,6 +87,34 @@ __device__ __forceinline__ double wf_log_i0(double x) {
 #pragma unroll
   for (int k = kWfI0AsymTerms; k >= 1; --k) acc = u * ((double)((2 * k - 1) * (2 * k - 1)) / (double)k) * (1.0 + acc);
   return x - 0.5 * log(kWfTwoPi * x) + log1p(acc);
+}
+
+// rho(x) = I1(x) / I0(x), x >= 0: d ln I0 / dx, in [0, 1), rho(0) = 0 exactly, no overflow for any finite x.  Below the switch point:
+// (x / 2) S1 / S0 with S0 = sum_{k >= 0} q^k / (k!)^2, S1 = sum_{k >= 0} q^k / (k! (k + 1)!), q = x^2 / 4 (positive terms; the stopping
+// rule and the cap of wf_log_i0).  From the switch point on: the ratio of the two 16-term series in 1 / (8 x), I0 with the factors
+// (2 m - 1)^2 / (8 x m), I1 with ((2 m - 1)^2 - 4) / (8 x m) (the first one is -3 / (8 x)); e^x / sqrt(2 pi x) cancels.
+__device__ __forceinline__ double wf_i1_over_i0(double x) {
+  if (x < kWfI0Switch) {
+    const double q = 0.25 * x * x;
+    double t0 = 1.0, t1 = 1.0, s0 = 1.0, s1 = 1.0;
+#pragma unroll
+    for (int k = 1; k <= kWfI0PowerTerms; ++k) {
+      t0 *= q * (1.0 / (double)(k * k));  // (unrolled: the reciprocals are constants)
+      t1 *= q * (1.0 / (double)(k * (k + 1)));
+      s0 += t0;
+      s1 += t1;
+      if (t0 <= s0 * 0x1p-60) break;
+    }
+    return (0.5 * x) * (s1 / s0);
+  }
+  const double u = 0.125 / x;
+  double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+  for (int k = kWfI0AsymTerms; k >= 1; --k) {
+    a0 = u * ((double)((2 * k - 1) * (2 * k - 1)) / (double)k) * (1.0 + a0);
+    a1 = u * ((double)((2 * k - 1) * (2 * k - 1) - 4) / (double)k) * (1.0 + a1);
+  }
+  return (1.0 + a1) / (1.0 + a0);
 }
 
 }  // namespace npf

@@ -15,12 +15,9 @@
 // outputs.  No atomics anywhere: a second call on the same inputs gives the same bits.
 //
 // Workspace, doubles, per row: [hh, gg, Re c_0/, Im c_0/, (Re c_j, Im c_j) for j < JC * chunks].
-#include "waveform_common.hpp"  // kWfJC, kWfThreads, kWfMaxTau, kWfTwoPi, wf_chunks, block_sum_store; kWfLlThreads, wf_log_i0
+#include "waveform_common.hpp"  // kWfJC, kWfThreads, kWfBwdThreads, kWfBwdMaxGridY, kWfMaxTau, kWfTwoPi, wf_chunks, block_sum_store; kWfLlThreads, wf_log_i0
 
 namespace npf {
-
-constexpr int kWfBwdThreads = 256;  // points per workgroup pass of the backward launch
-constexpr int kWfBwdMaxGridY = 1024;
 
 template <int JC, int THREADS>
 __global__ __launch_bounds__(THREADS) void waveform_corr_kernel(const float* __restrict__ h, int h_ld, const float* __restrict__ g,

@@ -677,6 +677,181 @@ def waveform_loglike_network(h: torch.Tensor, data: torch.Tensor, response: torc
     return WaveformLogLikeNetwork(*(out[name] for name in LOGLIKE_NET_NAMES), ser)
 
 
+# ---- differentiable likelihoods (csrc/waveform_grad_kernels.hip) --------------
+class WaveformLnl(NamedTuple):
+    """What :func:`waveform_lnl` / :func:`waveform_lnl_network` return: the four likelihoods (float64, differentiable with respect to
+    ``h``) and the grid index of the maximum (int32, not differentiable; 0 without ``taus``)."""
+    lnl_marg: torch.Tensor     # [R]
+    lnl_max: torch.Tensor      # [R]
+    lnl_mix: torch.Tensor      # [B]
+    lnl_max_mix: torch.Tensor  # [B]
+    tau_index: torch.Tensor    # [R] int32
+
+
+def _lnl_forward(net, h_eval, data, weights, freqs, nv, response, delays, geo):
+    """The forward launches of ``npf_waveform_loglike_ex`` / ``npf_waveform_loglike_net_ex`` on prepared tensors -> (the five outputs,
+    the float64 [R, 4 + 2 n] coefficients the backward launch starts from)."""
+    lib = L.load()
+    dev = h_eval.device
+    dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    if net:
+        R, T, ld, B, D, wgt_rows, freq_rows, tau0, dtau, n_tau = geo
+        ws = _match_workspace(dev, int(lib.npf_waveform_loglike_net_workspace_bytes(R, D, n_tau)))
+    else:
+        R, T, ld, B, wgt_rows, freq_rows, tau0, dtau, n_tau = geo
+        ws = _match_workspace(dev, int(lib.npf_waveform_loglike_workspace_bytes(R, n_tau)))
+    saved = torch.empty((R, int(lib.npf_waveform_loglike_saved_doubles(n_tau))), dtype=torch.float64, device=dev)
+    marg, mx = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
+    mix, mxm = (torch.empty((B,), dtype=torch.float64, device=dev) for _ in range(2))
+    idx = torch.empty((R,), dtype=torch.int32, device=dev)
+    head = (L.ptr(h_eval), ld, L.ptr(data), L.ptr(weights), wgt_rows, L.ptr(freqs), freq_rows, _iptr(nv) if nv is not None else None)
+    outs = (None, None, None, mx.data_ptr(), marg.data_ptr(), idx.data_ptr(), None, None, mix.data_ptr(), mxm.data_ptr())
+    if net:
+        L.check(lib.npf_waveform_loglike_net_ex(*head, dptr(delays), dptr(response), R, B, D, T, tau0, dtau, n_tau, *outs, None, None,
+                                                None, saved.data_ptr(), ws.data_ptr(), L.stream_ptr()), "npf_waveform_loglike_net_ex")
+    else:
+        L.check(lib.npf_waveform_loglike_ex(*head, R, B, T, tau0, dtau, n_tau, *outs, saved.data_ptr(), ws.data_ptr(), L.stream_ptr()),
+                "npf_waveform_loglike_ex")
+    return (marg, mx, mix, mxm, idx), saved
+
+
+def _lnl_backward(net, tensors, geo, n_bcast, src_shape, grads):
+    """One ``npf_waveform_loglike_bwd`` / ``npf_waveform_loglike_net_bwd`` launch -> the gradient of ``src``, written whole."""
+    h_eval, data, weights, freqs, nv, response, delays, marg, mx, mix, mxm, idx, saved = tensors
+    d_src = torch.empty(src_shape, dtype=torch.float32, device=h_eval.device)  # (written whole: no memset)
+    if all(g is None for g in grads):
+        return d_src.zero_()
+    grads = [g.to(torch.float64).contiguous() if g is not None else None for g in grads]
+    dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    head = (L.ptr(h_eval), geo[2], L.ptr(data), L.ptr(weights), geo[-5], L.ptr(freqs), geo[-4], _iptr(nv) if nv is not None else None)
+    tail = (geo[-3], geo[-2], geo[-1], _iptr(idx), saved.data_ptr(), marg.data_ptr(), mx.data_ptr(), mix.data_ptr(), mxm.data_ptr(),
+            *(dptr(g) for g in grads), n_bcast, L.ptr(d_src), src_shape[2], L.stream_ptr())
+    lib = L.load()
+    if net:
+        L.check(lib.npf_waveform_loglike_net_bwd(*head, dptr(delays), dptr(response), geo[0], geo[3], geo[4], geo[1], *tail),
+                "npf_waveform_loglike_net_bwd")
+    else:
+        L.check(lib.npf_waveform_loglike_bwd(*head, geo[0], geo[3], geo[1], *tail), "npf_waveform_loglike_bwd")
+    return d_src
+
+
+class _WaveformLnlFn(torch.autograd.Function):
+    """The four likelihoods of the rows of ``h_eval`` under ``data`` (``npf_waveform_loglike_ex``, which keeps the row coefficients
+    ``q_j`` in double) and their gradient with respect to ``src`` (one ``npf_waveform_loglike_bwd`` launch): ``src`` is ``h_eval``
+    itself (``n_bcast`` = 1) or the [n_bcast * R, T, ld] samples whose mean over the ``n_bcast`` row blocks ``h_eval`` holds."""
+
+    @staticmethod
+    def forward(ctx, src, h_eval, data, weights, freqs, nv, geo, n_bcast):
+        outs, saved = _lnl_forward(False, h_eval, data, weights, freqs, nv, None, None, geo)
+        ctx.save_for_backward(h_eval, data, weights, freqs, nv, None, None, *outs, saved)
+        ctx.cfg = (geo, n_bcast, tuple(src.shape))
+        ctx.mark_non_differentiable(outs[4])
+        ctx.set_materialize_grads(False)  # (an unused likelihood hands the launch a NULL, not a tensor of zeros)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_marg, d_max, d_mix, d_max_mix, _):
+        geo, n_bcast, src_shape = ctx.cfg
+        d_src = _lnl_backward(False, ctx.saved_tensors, geo, n_bcast, src_shape, (d_marg, d_max, d_mix, d_max_mix))
+        return d_src, None, None, None, None, None, None, None
+
+
+class _WaveformLnlNetworkFn(torch.autograd.Function):
+    """:class:`_WaveformLnlFn` over the network sums (``npf_waveform_loglike_net_ex`` / ``npf_waveform_loglike_net_bwd``)."""
+
+    @staticmethod
+    def forward(ctx, src, h_eval, data, response, delays, weights, freqs, nv, geo, n_bcast):
+        outs, saved = _lnl_forward(True, h_eval, data, weights, freqs, nv, response, delays, geo)
+        ctx.save_for_backward(h_eval, data, weights, freqs, nv, response, delays, *outs, saved)
+        ctx.cfg = (geo, n_bcast, tuple(src.shape))
+        ctx.mark_non_differentiable(outs[4])
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_marg, d_max, d_mix, d_max_mix, _):
+        geo, n_bcast, src_shape = ctx.cfg
+        d_src = _lnl_backward(True, ctx.saved_tensors, geo, n_bcast, src_shape, (d_marg, d_max, d_mix, d_max_mix))
+        return d_src, None, None, None, None, None, None, None, None, None
+
+
+def _lnl_rows(who, h, n_bcast, mean):
+    """The ``n_bcast`` / ``mean`` rules of :func:`waveform_mismatch` -> the tensor the likelihood is evaluated on (not yet detached)."""
+    if isinstance(n_bcast, bool) or not isinstance(n_bcast, int) or n_bcast < 1:
+        raise ValueError(f"n_bcast must be a host int >= 1, got {n_bcast!r}")
+    if n_bcast > 1 and mean is None:
+        raise ValueError(f"n_bcast > 1 evaluates {who} on `mean`, the mean of the n_bcast samples h holds: give it")
+    h_shape = tuple(getattr(h, "shape", ()))
+    if mean is not None:
+        if len(h_shape) != 3 or h_shape[0] % n_bcast != 0 or h_shape[2] < 2:
+            raise ValueError(f"h must have shape [n_bcast * R, T, >= 2] with n_bcast={n_bcast}, got {list(h_shape)}")
+        if not isinstance(mean, torch.Tensor) or mean.dim() != 3 or tuple(mean.shape[:2]) != (h_shape[0] // n_bcast, h_shape[1]):
+            raise ValueError(f"mean must have shape [R={h_shape[0] // n_bcast}, T={h_shape[1]}, >= 2], got "
+                             f"{list(mean.shape) if isinstance(mean, torch.Tensor) else type(mean).__name__}")
+    return h if mean is None else mean
+
+
+def waveform_lnl(h: torch.Tensor, data: torch.Tensor, weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None,
+                 taus=None, n_valid: Optional[torch.Tensor] = None, n_bcast: int = 1, mean: Optional[torch.Tensor] = None) -> WaveformLnl:
+    """``lnl_marg``, ``lnl_max`` [R], ``lnl_mix``, ``lnl_max_mix`` [B] and ``tau_index`` of :func:`waveform_loglike` (same arguments,
+    same bits), the four likelihoods differentiable with respect to ``h``: the objective a waveform surrogate is trained on when it
+    is to be used as the template in ``ln Lambda``.  The forward is the two launches of ``npf_waveform_loglike`` plus one that keeps
+    the coefficients ``q_j = p_j I1 / I0 (x_j) conj(u_j)`` of every row in double; the backward is ONE ``npf_waveform_loglike_bwd``
+    launch, the adjoint of the correlation launch, that forms the upstream scalars itself and writes the whole gradient of ``h``
+    [.., T, ld] (``include/npf_hip.h`` has the formulae).  The gradient of ``lnl_marg`` / ``lnl_mix`` is exact, through the time
+    marginal; that of ``lnl_max`` / ``lnl_max_mix`` is taken at the grid time the forward found (a tie: at the smaller index, a
+    subgradient).  Entries 2 .. ld - 1 of a point, removed and padded points and rows with ``hh == 0`` get exact zeros.  No gradient
+    with respect to ``data``, ``weights`` or ``freqs``: one of them with ``requires_grad`` is a ``ValueError``.  No double backward.
+    ``n_bcast`` / ``mean``: as in :func:`waveform_mismatch`.  No host sync; the workspace is the one of :func:`waveform_match`, so
+    inside a captured graph the call needs one earlier call at these sizes."""
+    h_eval = _lnl_rows("the likelihood", h, n_bcast, mean)
+    geo = check_loglike_args(getattr(h_eval, "shape", ()), data, weights, freqs, taus)
+    for t, what in ((data, "data"), (weights, "weights"), (freqs, "freqs")):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"waveform_lnl has no gradient with respect to {what}: detach it")
+    for t in (h, mean, data, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    n_tau, B = geo[8], geo[3]
+    h = h.contiguous()
+    h_eval = h.detach() if mean is None else mean.detach().contiguous()
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and n_tau > 0 else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    return WaveformLnl(*_WaveformLnlFn.apply(h, h_eval, data.detach().contiguous(), weights, freqs, nv, geo, n_bcast))
+
+
+def waveform_lnl_network(h: torch.Tensor, data: torch.Tensor, response: torch.Tensor, delays: Optional[torch.Tensor] = None,
+                         weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None, taus=None,
+                         n_valid: Optional[torch.Tensor] = None, n_bcast: int = 1, mean: Optional[torch.Tensor] = None) -> WaveformLnl:
+    """:func:`waveform_lnl` of the coherent network likelihood: the values of :func:`waveform_loglike_network` (same arguments, same
+    bits), differentiable with respect to ``h``.  One sum over the grid is shared by the detectors; the backward launch
+    (``npf_waveform_loglike_net_bwd``) walks the detectors that are live at a point in ascending order.  No gradient with respect
+    to ``data``, ``response``, ``delays``, ``weights`` or ``freqs`` (``requires_grad`` on one of them: ``ValueError``)."""
+    h_eval = _lnl_rows("the likelihood", h, n_bcast, mean)
+    geo = check_loglike_network_args(getattr(h_eval, "shape", ()), data, response, delays, weights, freqs, taus)
+    for t, what in ((data, "data"), (response, "response"), (delays, "delays"), (weights, "weights"), (freqs, "freqs")):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"waveform_lnl_network has no gradient with respect to {what}: detach it")
+    for t in (h, mean, data, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    for t, what in ((response, "response"), (delays, "delays")):
+        if t is not None and (not t.is_cuda or t.device != h.device):
+            raise ValueError(f"{what} must live on the device of h ({h.device}), got {t.device}: the kernel reads it there")
+    n_tau, B = geo[9], geo[3]
+    h = h.contiguous()
+    h_eval = h.detach() if mean is None else mean.detach().contiguous()
+    delays = delays.detach().contiguous() if delays is not None else None
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and (n_tau > 0 or delays is not None) else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    return WaveformLnl(*_WaveformLnlNetworkFn.apply(h, h_eval, data.detach().contiguous(), response.detach().contiguous(), delays,
+                                                    weights, freqs, nv, geo, n_bcast))
+
+
 # ---- distance-marginalised likelihood (csrc/waveform_dist_kernels.hip) --------------
 DIST_SC = 16             # NPF_DIST_SC: scales per workgroup of the scale launch
 DIST_MAX_SCALES = 4096   # NPF_DIST_MAX_SCALES

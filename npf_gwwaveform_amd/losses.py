@@ -21,7 +21,7 @@ from torch.distributions.kl import kl_divergence
 
 from . import functional as FN
 
-__all__ = ["CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LightTailPareto", "sum_log_prob"]
+__all__ = ["CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LogLikeLoss", "LightTailPareto", "sum_log_prob"]
 
 
 def sum_log_prob(prob, sample):
@@ -213,4 +213,77 @@ class MismatchLoss(nn.Module):
         if self.reduction is not None:
             mm = mm.mean(0) if self.reduction == "mean" else mm.sum(0)
         loss = self.lam * mm
+        return loss if self.base is None else self.base(pred_outputs, Y_trgt) + loss
+
+
+class LogLikeLoss(nn.Module):
+    """``base(pred_outputs, Y_trgt) + lam * (-lnl)``: a likelihood objective with minus the matched-filter log likelihood ratio of
+    the targets' own signal under the predicted waveform added (:meth:`~npf_gwwaveform_amd.neuralproc.HeadDistribution.lnl`).
+    The data are the zero-noise injection of the targets, ``d = A' e^{i phi'}`` from ``Y_trgt`` [B, T, 2] = (amplitude, phase),
+    formed without gradient with ``cos`` / ``sin`` in double and rounded once to fp32, plus ``noise`` where given.  Unlike the
+    mismatch, ``ln Lambda`` sees amplitude errors, is differentiated through the marginal over the arrival-time grid, and
+    (``statistic="marg"``) is the mixture over the latent samples a latent model should raise.  No counterpart in the reference.
+
+    ``base``: as in :class:`MismatchLoss`; ``None``: the likelihood ratio alone.  It depends on the predicted amplitude and phase
+    only, so without ``base`` the predictive scale sigma receives NO gradient and is left wherever it is.  ``lam``: the weight (a
+    host float).  ``weights`` (``4 df / S_n(f)``; ``None``: ones) and ``freqs`` (Hz): [T] or [B, T] tensors, and ``noise`` [B, T, 2] =
+    (Re, Im) added to the injection, kept as non-persistent buffers: they follow ``.to(device)`` and stay out of the
+    ``state_dict``.  A caller overwrites them in place between steps (``loss.noise.copy_(n)``); a captured training step reads
+    them as static inputs.  ``taus = (tau0, dtau, n_tau)``: the grid of arrival times (needs ``freqs``), host numbers that are part
+    of a captured step.  ``statistic``: ``"marg"`` -- ``lnl``, phase, time and latent samples marginalised -- or ``"max"`` --
+    ``lnl_max_mix``.  ``of``: ``"samples"`` or ``"mean"`` (the likelihood of the mixture mean).  ``reduction`` ("mean" | "sum" |
+    None) reduces the per-task term over the tasks like the other losses.  Padded targets are taken from the distribution's
+    ``n_trgt``.  The model must predict (amplitude, phase): ``y_dim != 2`` is a ``ValueError``."""
+
+    def __init__(self, base=None, lam=1.0, weights=None, freqs=None, taus=None, statistic="marg", of="samples", noise=None,
+                 reduction="mean"):
+        super().__init__()
+        if base is not None and not isinstance(base, nn.Module):
+            raise ValueError(f"base must be None or a loss module, got {type(base).__name__}")
+        if isinstance(lam, (bool, torch.Tensor)) or not isinstance(lam, (int, float)) or not np.isfinite(lam):
+            raise ValueError(f"lam must be a finite host float, got {lam!r}")
+        if statistic not in ("marg", "max"):
+            raise ValueError(f"statistic must be 'marg' or 'max', got {statistic!r}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        if reduction not in ("mean", "sum", None):
+            raise ValueError(f"Unknown {reduction}")
+        for t, what in ((weights, "weights"), (freqs, "freqs")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.dtype != torch.float32:
+                raise ValueError(f"{what} must be None or a float32 tensor of shape [T] or [B, T], got "
+                                 f"{(list(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if t.requires_grad:
+                raise ValueError(f"the likelihood has no gradient with respect to {what}: detach it")
+        if noise is not None:
+            if not isinstance(noise, torch.Tensor) or noise.dim() != 3 or noise.shape[2] != 2 or noise.dtype != torch.float32:
+                raise ValueError(f"noise must be None or a float32 tensor of shape [B, T, 2] = (Re, Im), got "
+                                 f"{(list(noise.shape), noise.dtype) if isinstance(noise, torch.Tensor) else type(noise).__name__}")
+            if noise.requires_grad:
+                raise ValueError("the likelihood has no gradient with respect to noise: detach it")
+        self.taus = FN.check_taus(taus, freqs is not None)
+        self.base, self.lam, self.statistic, self.of, self.reduction = base, float(lam), statistic, of, reduction
+        self.register_buffer("weights", weights, persistent=False)
+        self.register_buffer("freqs", freqs, persistent=False)
+        self.register_buffer("noise", noise, persistent=False)
+
+    def injection(self, Y_trgt):
+        """The data [B, T, 2] = (Re, Im): ``A' e^{i phi'}`` of ``Y_trgt``, plus ``noise``; fp32, without gradient."""
+        with torch.no_grad():
+            a, p = Y_trgt[..., 0].double(), Y_trgt[..., 1].double()
+            d = torch.stack([a * torch.cos(p), a * torch.sin(p)], -1)
+            if self.noise is not None:
+                d = d + self.noise.double()
+            return d.float()
+
+    def forward(self, pred_outputs, Y_trgt):
+        p_yCc = pred_outputs[0]
+        if not hasattr(p_yCc, "lnl"):
+            raise ValueError(f"LogLikeLoss needs the predictive distribution of this package's models, got {type(p_yCc).__name__}")
+        m = p_yCc.lnl(self.injection(Y_trgt), weights=self.weights, freqs=self.freqs, taus=self.taus, of=self.of)
+        nll = -(m.lnl if self.statistic == "marg" else m.lnl_max_mix)  # [B] float64
+        if self.reduction is not None:
+            nll = nll.mean(0) if self.reduction == "mean" else nll.sum(0)
+        loss = (self.lam * nll).float()
         return loss if self.base is None else self.base(pred_outputs, Y_trgt) + loss

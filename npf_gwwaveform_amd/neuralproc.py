@@ -137,6 +137,15 @@ class NetworkDistanceLogLike(NamedTuple):
     base: NetworkLogLike
 
 
+class Lnl(NamedTuple):
+    """The differentiable likelihoods of :meth:`HeadDistribution.lnl` / :meth:`HeadDistribution.lnl_network`, float64, with the bits
+    of :meth:`HeadDistribution.loglike` / :meth:`HeadDistribution.loglike_network`."""
+    lnl: torch.Tensor          # [B] lnl_marg marginalised over the latent samples: log-mean-exp
+    lnl_marg: torch.Tensor     # [n_z, B] ([1, B] for ``of="mean"``) phase and grid times marginalised
+    lnl_max: torch.Tensor      # [n_z, B] ([1, B]) phase and grid times maximised
+    lnl_max_mix: torch.Tensor  # [B] the log-mean-exp of lnl_max
+
+
 def _as_loglike(m, taus, lead) -> LogLike:
     """A ``functional.WaveformLogLike`` (every name but ``tau_index`` without ``taus``) with its per-row entries shaped ``lead``."""
     tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
@@ -268,8 +277,9 @@ class HeadDistribution(Independent):
         Two ``npf_waveform_loglike`` launches; inference only, no host sync, so a ``query`` and its ``loglike`` can be captured in
         one graph (call once at the sizes before capturing: the workspace is allocated then).
         Distance / amplitude marginalisation is :meth:`loglike_distance`, which returns this result as its ``base``.
-        Out of scope: gradients of the likelihood; marginalising the head's per-point sigma (only the latent samples are
-        marginalised); non-uniform time priors; sub-grid time interpolation."""
+        Inference only; the gradients of this likelihood, for training on ``ln Lambda``, come from its differentiable twin :meth:`lnl`.
+        Out of scope: marginalising the head's per-point sigma (only the latent samples are marginalised);
+        non-uniform time priors; sub-grid time interpolation."""
         if self._y_dim != 2:
             raise ValueError(f"loglike needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
         if of not in ("samples", "mean"):
@@ -302,8 +312,9 @@ class HeadDistribution(Independent):
         ``npf_waveform_loglike_net`` launches; inference only, no host sync, so a ``query`` and its ``loglike_network`` can be
         captured in one graph (call once at the sizes before capturing) and replayed after ``response`` / ``delays`` were
         overwritten in place.  The distance marginalisation of this likelihood is :meth:`loglike_network_distance`.
+        Inference only; the gradients of this likelihood come from its differentiable twin :meth:`lnl_network`.
         Out of scope: antenna patterns and delays from a sky position (the caller's, from their GW library); a sky grid per task;
-        gradients; sub-grid time interpolation."""
+        sub-grid time interpolation."""
         if self._y_dim != 2:
             raise ValueError(f"loglike_network needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
         if of not in ("samples", "mean"):
@@ -399,6 +410,50 @@ class HeadDistribution(Independent):
         n_a = scales.shape[-1]
         return (m.lnl_dist_mix, m.lnl_dist.view(lead), m.scale_hat.view(lead), m.lnl_amp_max.view(lead), m.scale_index.view(lead),
                 scale_map, m.post.view(*lead, n_a) if m.post is not None else None, m.post_mix)
+
+    def lnl(self, data, weights=None, freqs=None, taus=None, of="samples") -> Lnl:
+        """The likelihoods of :meth:`loglike` (same arguments, same bits) as a training objective -> :class:`Lnl`: differentiable
+        with respect to the raw decoder output, so ``(-p.lnl(d, ...).lnl).mean().backward()`` reaches the model's parameters --
+        the surrogate is trained on the quantity it is used in.  Unlike the mismatch, ``ln Lambda`` sees amplitude errors; the
+        gradient of ``lnl_marg`` and of the mixture ``lnl`` is exact, through the marginal over the grid of arrival times and over
+        the latent samples; that of ``lnl_max`` / ``lnl_max_mix`` is taken at the grid time the forward found (a tie: the earlier
+        one, a subgradient).  It flows into the amplitude and phase entries only: the scale entries of the raw output, padded
+        targets (``n_trgt``), removed points and rows with ``<h|h> = 0`` receive exact zeros, so a loss made of the likelihood
+        alone does not train sigma (:class:`~npf_gwwaveform_amd.losses.LogLikeLoss` adds a base loss for that).  ``of="mean"``:
+        the likelihood of the mixture mean ([1, B]; one moments-only ``npf_mixture_summary`` launch); every latent sample receives
+        ``1 / n_z`` of the task's gradient.  Forward: the launches of ``npf_waveform_loglike_ex``; backward: one
+        ``npf_waveform_loglike_bwd`` launch.  No host sync: the call and its backward sit in a captured training step (call once
+        at the sizes before capturing).  :meth:`loglike` stays the inference call: it returns everything else and builds no graph."""
+        return self._lnl(None, data, None, None, weights, freqs, taus, of)
+
+    def lnl_network(self, data, response, delays=None, weights=None, freqs=None, taus=None, of="samples") -> Lnl:
+        """:meth:`lnl` of the coherent network likelihood: the values of :meth:`loglike_network` (same arguments, same bits),
+        differentiable with respect to the raw decoder output (``npf_waveform_loglike_net_ex`` / ``npf_waveform_loglike_net_bwd``).
+        No gradient reaches ``data``, ``response``, ``delays``, ``weights`` or ``freqs``."""
+        return self._lnl("network", data, response, delays, weights, freqs, taus, of)
+
+    def _lnl(self, network, data, response, delays, weights, freqs, taus, of) -> Lnl:
+        who = "lnl_network" if network else "lnl"
+        if self._y_dim != 2:
+            raise ValueError(f"{who} needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        if network:
+            FN.check_loglike_network_args((rows, T, ld), data, response, delays, weights, freqs, taus)
+        else:
+            FN.check_loglike_args((rows, T, ld), data, weights, freqs, taus)
+        suff = self._suff.reshape(n_z * B, T, 4)
+        extra = {}
+        if of == "mean":
+            extra = dict(n_bcast=n_z, mean=FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk, n_valid=self._n_trgt)[0])
+        if network:
+            m = FN.waveform_lnl_network(suff, data, response, delays, weights, freqs, taus, n_valid=self._n_trgt, **extra)
+        else:
+            m = FN.waveform_lnl(suff, data, weights, freqs, taus, n_valid=self._n_trgt, **extra)
+        lead = (rows // B, B)
+        return Lnl(m.lnl_mix, m.lnl_marg.view(lead), m.lnl_max.view(lead), m.lnl_max_mix)
 
     def mismatch(self, Y_ref, weights=None, freqs=None, taus=None, of="samples") -> torch.Tensor:
         """``mismatch`` of :meth:`match` (same arguments, same bits) as a training objective -> [n_z, B], or [1, B] for
