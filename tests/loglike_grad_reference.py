@@ -12,7 +12,8 @@ direct sines and exactly rounded sums over t and j (``math.fsum``); ``recurrence
 of ``jc`` shifts, one direct sine / cosine pair per chunk, z <- z s inside, the kernels' ln I0 and I1 / I0 schemes.  Both return a
 ``Parts`` object; ``grad_of`` turns it into (d_h [R, T, 2], S [R, T]) for one set of upstream gradients, which is linear and cheap, so
 the tests evaluate every upstream combination on one ``Parts``.  tests/test_loglike_grad_host.py checks ``closed_form`` against
-central differences of the definition in 50-digit arithmetic.
+central differences of the definition in 50-digit arithmetic.  ``saved_reference`` is the row of coefficients the forward keeps for the
+backward (``waveform_loglike_coef_kernel``), with its own derived gate (``saved_gates``).
 
 Gate per element (``gate_ratio``):  |d| <= 2^-23 (1 + 2^-20) |ref| + (1e-10 S_r + 1e-12) S_{r,t},  S_r = ``loglike_reference.scale_of``,
 S_{r,t} = (|g_marg| + |g_max|) sum_k |C_k| w_{k,t} (|d_{k,t}| + |A_t|) max(1, |A_t|).  The first term is the one fp32 rounding of the
@@ -120,8 +121,10 @@ def _amplitude(h, dets):
     return torch.where(live_any, h.detach().cpu().double()[..., 0], torch.zeros_like(dets[0][8]))
 
 
-def _assemble(args, dets, Bn, K, Qm_of, p_rho):
-    """The parts from the network sums K [R, n]; ``Qm_of(q, f)`` sums q_j e^{i 2 pi f tau_j}, ``p_rho(x)`` gives p_j rho(x_j)."""
+def _assemble(args, dets, Bn, K, Qm_of, p_rho, tau_index=None):
+    """The parts from the network sums K [R, n]; ``Qm_of(q, f)`` sums q_j e^{i 2 pi f tau_j}, ``p_rho(x)`` gives p_j rho(x_j).
+    ``tau_index`` (an int or [R]): the grid index the ``lnl_max`` direction Mx is taken at, in place of the reference's own
+    maximiser -- what a near tie leaves open; the likelihoods stay those of the maximum.  ``ref`` also gets "q" [R, n] (q_j)."""
     taus = args["taus"]
     HH = RN._fsum_cols([(d[5].real ** 2 + d[5].imag ** 2) * d[2] for d in dets])
     DD = RN._fsum_cols([d[3] for d in dets])
@@ -131,6 +134,10 @@ def _assemble(args, dets, Bn, K, Qm_of, p_rho):
     u = torch.where(x > 0, K / torch.where(x > 0, x, torch.ones_like(x)), torch.zeros_like(K))
     q = p_rho(x) * u.conj()
     q = torch.where(ref["degenerate"].view(-1, 1), torch.zeros_like(q), q)
+    ref["q"] = q
+    if tau_index is not None:
+        forced = torch.as_tensor(tau_index, dtype=torch.long).expand(ref["tau_index"].shape)
+        ref["tau_index"] = torch.where(ref["degenerate"], torch.zeros_like(forced), forced)
     f = dets[0][4]
     for d in dets[1:]:  # the frequency of a point that is live for any detector
         f = torch.where(f != 0, f, d[4])
@@ -146,9 +153,9 @@ def _assemble(args, dets, Bn, K, Qm_of, p_rho):
     return Parts(Qm, Mx, Ew, wc2, s_k, A, ref, Bn)
 
 
-def closed_form(args):
+def closed_form(args, tau_index=None):
     """``Parts`` of one input set (the keys of ``loglike_reference.call_args`` or ``loglike_net_reference.call_args``) with direct
-    sines and exactly rounded sums."""
+    sines and exactly rounded sums (``tau_index``: see ``_assemble``)."""
     dets, Bn = _detectors(args)
     tau = _grid(args["taus"])
     K = None
@@ -163,7 +170,7 @@ def closed_form(args):
     def p_rho(x):
         return torch.softmax(R1.log_i0(x), 1) * rho(x)
 
-    return _assemble(args, dets, Bn, K, Qm_of, p_rho)
+    return _assemble(args, dets, Bn, K, Qm_of, p_rho, tau_index)
 
 
 def recurrence(args, jc=16, x_s=24.0):
@@ -201,6 +208,46 @@ def recurrence(args, jc=16, x_s=24.0):
         return torch.tensor(rows, dtype=torch.float64)
 
     return _assemble(args, dets, Bn, K, Qm_of, p_rho)
+
+
+# ---- the coefficients the forward keeps for the backward ------------------------------------------------------------------------------
+def saved_reference(parts):
+    """float64 [R, 4 + 2 n] of what ``waveform_loglike_coef_kernel`` writes: hh, Re / Im conj(u_{j*}), 0, (Re q_j, Im q_j) j < n;
+    rows with hh == 0 are all zero."""
+    ref = parts.ref
+    K, x, q = ref["K"], ref["x"], ref["q"]
+    idx = ref["tau_index"].view(-1, 1)
+    kb, xb = K.gather(1, idx)[:, 0], x.gather(1, idx)[:, 0]
+    ub = torch.where(xb > 0, kb / torch.where(xb > 0, xb, torch.ones_like(xb)), torch.zeros_like(kb)).conj()
+    head = torch.stack([ref["hh"], ub.real, ub.imag, torch.zeros_like(xb)], 1)
+    out = torch.cat([head, torch.view_as_real(q.resolve_conj()).reshape(q.shape[0], -1)], 1)
+    return torch.where(ref["degenerate"].view(-1, 1), torch.zeros_like(out), out)
+
+
+def saved_gates(parts):
+    """(delta_K [R, n], gate of q [R, n]).  q_j = p_j rho(x_j) conj(u_j): a relative error of p_j is an absolute error of L_j, which
+    the forward suites gate at delta_L = 1e-10 S_r + 1e-12; ``loglike_reference.ratios`` gates series[j] = x_j / sqrt(hh) at 1e-10
+    relative + 1e-12, which is delta_K_j = 1e-10 x_j + 1e-12 sqrt(hh) on K_j; d(rho u) = rho' dx u + rho du with rho' <= 1 / 2 and
+    rho / x <= 1 / 2, so an absolute error of K_j is at most half of it on rho u; one rounding of the double that is stored:
+        |dq_j| <= p_j (delta_L + delta_K_j / 2) + 2^-52 |q_j|."""
+    ref = parts.ref
+    x, q = ref["x"], ref["q"]
+    deg = ref["degenerate"].view(-1, 1)
+    p = torch.where(deg, torch.zeros_like(x), torch.softmax(R1.log_i0(x), 1))
+    d_L = (1e-10 * R1.scale_of(ref) + 1e-12).view(-1, 1)
+    d_K = 1e-10 * x + 1e-12 * ref["hh"].sqrt().view(-1, 1)
+    return d_K, p * (d_L + 0.5 * d_K) + 2.0 ** -52 * q.abs()
+
+
+def saved_ratio(got, parts):
+    """Worst |q_j - reference| / gate over ``got`` [R, 4 + 2 n] (the coefficient columns only)."""
+    want = saved_reference(parts)
+    _, gate = saved_gates(parts)
+    d = (got.detach().cpu().double() - want)[:, 4:].abs().view(want.shape[0], -1, 2)
+    d = (d[..., 0] ** 2 + d[..., 1] ** 2).sqrt()
+    r = torch.where(d == 0, torch.zeros_like(d), d / gate)
+    r = torch.where(torch.isfinite(d), r, torch.full_like(r, math.inf))
+    return float(r.max()) if r.numel() else 0.0
 
 
 # ---- upstream gradients, the gradient, the gate -------------------------------------------------------------------------------------
