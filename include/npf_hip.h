@@ -24,6 +24,8 @@
  *                        reference counterpart)
  *   npf_waveform_match_ex/_bwd  the same with the unrounded row scalars kept, and the gradient of the match with respect to the
  *                        predicted amplitude and phase (training on the mismatch; no reference counterpart)
+ *   npf_waveform_match_bank  the match of every predicted waveform against every template of one shared bank, the contraction on
+ *                        the double-precision matrix instruction (inference; no reference counterpart)
  *   npf_waveform_loglike  matched-filter SNR and log likelihood of complex data under the predicted waveforms, phase and arrival
  *                        time maximised or marginalised, and marginal over the latent samples (inference; no reference counterpart)
  *   npf_waveform_loglike_net  the coherent likelihood of a detector network: per-detector weights, delays and complex responses,
@@ -754,6 +756,39 @@ int npf_waveform_match_bwd(const float *h, int32_t h_ld, const float *g, const f
                            int32_t freq_rows, const int32_t *n_valid, int32_t n_rows, int32_t n_tasks, int32_t pts, double tau0,
                            double dtau, int32_t n_tau, const int32_t *tau_index, const double *saved, const float *d_match,
                            int32_t n_bcast, float *d_h, int32_t dh_ld, void *stream);
+
+/* ---- bank match: every predicted waveform against every template of one bank (csrc/waveform_bank_kernels.hip; no reference counterpart)
+ * h[n_rows][pts][h_ld] as in npf_waveform_match (entries 0 and 1 are A, phi; h_ld >= 2).  bank[n_bank][pts][2] = (A', phi') is ONE
+ * bank shared by all rows, so wgt[pts] (NULL: ones) and freq[pts] (NULL only when n_tau == 0) are single rows and there is no
+ * n_valid.  A point is removed unless 0 < w_t < +inf: nothing of it is read in h, bank or freq, NaN included; removed points are
+ * selected out (the operand panels are built from the live points alone), never multiplied in, so a call with removed points has
+ * the bits of the same call with those points cut out.  For row r, template g and tau_j = tau0 + j dtau, j < n_tau:
+ *   hh_r = sum_t w_t A_{r,t}^2          gg_g = sum_t w_t A'_{g,t}^2
+ *   c_j[r,g] = sum_t w_t A_{r,t} A'_{g,t} exp(i (phi_{r,t} - phi'_{g,t} + 2 pi f_t tau_j))
+ *   match[r][g]     = max_j |c_j| / sqrt(hh_r gg_g)       tau_index[r][g] = the smallest j that attains it
+ *   phase[r][g]     = arg c_{j*}                          mismatch = 1 - match (formed in double, rounded once)
+ *   dot[r][g][2]    = c_{j*} as unrounded DOUBLES
+ *   best_index[r]   = the smallest g that attains max_g match[r][g] over the pairs whose match is not NaN, 0 if there is none
+ *   best_match[r]   = match[r][best_index[r]]
+ * n_tau == 0: the single candidate without the time term.  A pair with hh_r gg_g == 0 gets match = 0, mismatch = 1, tau_index = 0,
+ * phase = 0, dot = 0.  A NaN at a live point of row r reaches row r's outputs only, a NaN in template g column g only.
+ * Arithmetic: double throughout, from fp32 inputs widened exactly.  Launch 1 writes the operand panels u = w A e^{i phi}, v = A' e^{i
+ * phi'}, the per-point step e^{i 2 pi f dtau} and the start e^{i 2 pi f tau_c} of every chunk of NPF_WAVEFORM_JC shifts into
+ * `workspace` and reduces hh, gg in a fixed order.  Launch 2: one wavefront per (16 rows, 16 templates); per chunk it rotates its
+ * rows once per shift (start, then one complex rotation per further shift: the scheme of npf_waveform_match) and contracts
+ * K = 2 pts on v_mfma_f64_16x16x4_f64: Re c takes (Re u, Im u) against (Re v, Im v), Im c against (-Im v, Re v).  The running maximum
+ * of |c_j|^2, its first index and c there stay in registers: nothing of size [n_rows][n_bank][n_tau] is written.  Launch 3 (best_*
+ * only): one wavefront per row.  No atomics, fixed K and tile order: the same inputs give the same bits.  The host reads no device
+ * data: the call sits in a captured graph.  Outputs: each may be NULL, at least one must be given; every requested element is
+ * written.  workspace: npf_waveform_match_bank_workspace_bytes(...) bytes of device memory, 8-byte aligned.
+ * Status: NPF_EINVAL (nothing launched; -1 from the workspace function for the same sizes) for n_rows, n_bank or pts <= 0,
+ * n_rows > 2^24, n_bank > 2^20, h_ld < 2, n_tau outside [0, 65536], n_tau > 0 with freq == NULL, a NULL h, bank or workspace, all
+ * outputs NULL. */
+int64_t npf_waveform_match_bank_workspace_bytes(int32_t n_rows, int32_t n_bank, int32_t pts, int32_t n_tau);
+int npf_waveform_match_bank(const float *h, int32_t h_ld, const float *bank, const float *wgt, const float *freq,
+                            int32_t n_rows, int32_t n_bank, int32_t pts, double tau0, double dtau, int32_t n_tau,
+                            float *hh, float *gg, float *match, float *mismatch, int32_t *tau_index, float *phase,
+                            double *dot, int32_t *best_index, float *best_match, void *workspace, void *stream);
 
 /* ---- matched-filter log likelihood of complex data under the predicted waveforms (csrc/waveform_kernels.hip; no reference counterpart)
  * h, h_ld, wgt, wgt_rows, freq, freq_rows, n_valid, n_rows, n_tasks, pts, tau0, dtau, n_tau: as in npf_waveform_match; row

@@ -156,6 +156,9 @@ SIGNATURES = {
                                         _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "npf_waveform_match_bwd": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
                                          _p, _p, _p, _i32, _p, _i32, _p]),
+    "npf_waveform_match_bank_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "npf_waveform_match_bank": (C.c_int, [_p, _i32, _p, _p, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
+                                          _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "npf_waveform_loglike_workspace_bytes": (_i64, [_i32, _i32]),
     "npf_waveform_loglike": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
                                        _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -424,6 +424,97 @@ def _match_launch(h, g, weights, freqs, nv, geo, want, corr, saved) -> WaveformM
     return WaveformMatch(*(out[name] for name in MATCH_NAMES), c)
 
 
+# ---- bank match: every row against every template of one shared bank (csrc/waveform_bank_kernels.hip) ----
+BANK_NAMES = ("hh", "gg", "match", "mismatch", "tau_index", "phase", "best_index", "best_match")
+BANK_MAX_ROWS = 1 << 24
+BANK_MAX_BANK = 1 << 20
+
+
+class WaveformBankMatch(NamedTuple):
+    """What :func:`waveform_match_bank` returns; the entries that were not asked for are ``None``."""
+    hh: Optional[torch.Tensor]          # [R] sum_t w A^2
+    gg: Optional[torch.Tensor]          # [G] sum_t w A'^2
+    match: Optional[torch.Tensor]       # [R, G]
+    mismatch: Optional[torch.Tensor]    # [R, G]
+    tau_index: Optional[torch.Tensor]   # [R, G] int32
+    phase: Optional[torch.Tensor]       # [R, G]
+    best_index: Optional[torch.Tensor]  # [R] int32: the template of the largest match, the smallest index
+    best_match: Optional[torch.Tensor]  # [R] the match there
+    dot: Optional[torch.Tensor]         # [R, G, 2] float64: the unrounded correlation at the maximum (``dot=True``)
+
+
+def check_bank_want(want) -> tuple:
+    """``want`` as a tuple of names out of ``BANK_NAMES`` (may be empty: ``dot`` alone); anything else is a ValueError."""
+    if isinstance(want, str) or not isinstance(want, (tuple, list)):
+        raise ValueError(f"want must be a tuple / list of names out of {BANK_NAMES}, got {want!r}")
+    for w in want:
+        if w not in BANK_NAMES:
+            raise ValueError(f"want: unknown entry {w!r} (known: {BANK_NAMES})")
+    return tuple(want)
+
+
+def check_match_bank_args(h_shape, bank, weights=None, freqs=None, taus=None):
+    """The shapes and host values of a :func:`waveform_match_bank` call -> ``(R, T, h_ld, G, tau0, dtau, n_tau)``; ``ValueError`` for
+    anything that does not fit.  Reads shapes only, so it runs on tensors of any device: ``h_shape`` = [R, T, >= 2] with ``R <=
+    BANK_MAX_ROWS``, ``bank`` [G, T, 2] with ``G <= BANK_MAX_BANK``, ``weights`` / ``freqs`` ``None`` or [T] -- the bank is shared
+    by the rows, so there is one frequency grid -- and ``taus`` as in :func:`check_match_args`."""
+    h_shape = tuple(h_shape)
+    if len(h_shape) != 3 or h_shape[2] < 2 or h_shape[0] < 1 or h_shape[1] < 1:
+        raise ValueError(f"h must have shape [R, T, >= 2] (amplitude, phase first), got {list(h_shape)}")
+    R, T, ld = h_shape
+    if R > BANK_MAX_ROWS:
+        raise ValueError(f"h holds {R} rows; a bank match takes at most {BANK_MAX_ROWS}")
+    if not isinstance(bank, torch.Tensor) or bank.dim() != 3 or bank.shape[0] < 1 or tuple(bank.shape[1:]) != (T, 2):
+        raise ValueError(f"bank must have shape [G, T={T}, 2], got "
+                         f"{list(bank.shape) if isinstance(bank, torch.Tensor) else type(bank).__name__}")
+    G = bank.shape[0]
+    if G > BANK_MAX_BANK:
+        raise ValueError(f"bank holds {G} templates; a bank match takes at most {BANK_MAX_BANK}")
+    for t, what in ((weights, "weights"), (freqs, "freqs")):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (T,)):
+            raise ValueError(f"{what} must be None or a tensor of shape [T={T}] (one grid shared by the bank), got "
+                             f"{list(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    taus = check_taus(taus, freqs is not None)
+    tau0, dtau, n_tau = taus if taus is not None else (0.0, 0.0, 0)
+    return R, T, ld, G, tau0, dtau, n_tau
+
+
+def waveform_match_bank(h: torch.Tensor, bank: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                        freqs: Optional[torch.Tensor] = None, taus=None, want=BANK_NAMES, dot: bool = False) -> WaveformBankMatch:
+    """The match of EVERY predicted waveform ``h`` [R, T, >= 2] (amplitude, phase first) against EVERY template of ``bank``
+    [G, T, 2], one bank shared by the rows: ``c_j[r, g] = sum_t w A A' exp(i (phi - phi' + 2 pi f tau_j))`` over the grid of ``taus
+    = (tau0, dtau, n_tau)``, ``match[r, g] = max_j |c_j| / sqrt(hh_r gg_g)`` with ``tau_index`` the first index that attains it and
+    ``phase = arg c`` there, ``mismatch = 1 - match`` formed in double; ``best_index[r]`` is the template of the largest match that is
+    not NaN (the smallest index; 0 if there is none) and ``best_match[r]`` the match there.  ``weights`` (``None``: ones) and
+    ``freqs`` are [T]: a shared bank means a shared grid; a point whose weight is not in (0, inf) is removed, whatever the other
+    tensors hold there.  ``want``: the names out of ``BANK_NAMES`` to compute; ``dot=True`` adds the correlation at the maximum as
+    unrounded float64 [R, G, 2].  ``npf_waveform_match_bank``: the per-shift rotation is done once per row and the contraction runs
+    on the double-precision matrix instruction (``include/npf_hip.h`` has the contract); inference only (no autograd), no host sync,
+    deterministic; the workspace is the one of :func:`waveform_match`."""
+    want = check_bank_want(want)
+    R, T, ld, G, tau0, dtau, n_tau = check_match_bank_args(getattr(h, "shape", ()), bank, weights, freqs, taus)
+    if not want and not dot:
+        raise ValueError(f"want must name at least one of {BANK_NAMES} (or dot=True)")
+    for t in (h, bank, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    h, bank = h.detach().contiguous(), bank.detach().contiguous()
+    weights = weights.detach().contiguous() if weights is not None else None
+    freqs = freqs.detach().contiguous() if freqs is not None and n_tau > 0 else None
+    lib = L.load()
+    ws = _match_workspace(h.device, int(lib.npf_waveform_match_bank_workspace_bytes(R, G, T, n_tau)))
+    shape = {"hh": (R,), "gg": (G,), "best_index": (R,), "best_match": (R,)}
+    out = {name: (torch.empty(shape.get(name, (R, G)), dtype=torch.int32 if name.endswith("index") else torch.float32, device=h.device)
+                  if name in want else None) for name in BANK_NAMES}
+    d = torch.empty((R, G, 2), dtype=torch.float64, device=h.device) if dot else None
+    ptr = lambda name: out[name].data_ptr() if out[name] is not None else None  # noqa: E731
+    L.check(lib.npf_waveform_match_bank(L.ptr(h), ld, L.ptr(bank), L.ptr(weights), L.ptr(freqs), R, G, T, tau0, dtau, n_tau,
+                                        ptr("hh"), ptr("gg"), ptr("match"), ptr("mismatch"), ptr("tau_index"), ptr("phase"),
+                                        d.data_ptr() if d is not None else None, ptr("best_index"), ptr("best_match"), ws.data_ptr(),
+                                        L.stream_ptr()), "npf_waveform_match_bank")
+    return WaveformBankMatch(*(out[name] for name in BANK_NAMES), d)
+
+
 class _WaveformMismatchFn(torch.autograd.Function):
     """``mismatch`` [R] of the rows of ``h_eval`` against ``g`` (``npf_waveform_match_ex``, which keeps the unrounded row scalars) and
     its gradient with respect to ``src`` (``npf_waveform_match_bwd``, one launch that writes every element): ``src`` is ``h_eval``

@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlat
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "LogLike", "NetworkLogLike", "DistanceLogLike",
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "BankMatch", "LogLike", "NetworkLogLike", "DistanceLogLike",
            "NetworkDistanceLogLike", "Reweighted", "bootstrap_weights",
            "kfold_weights"]
 
@@ -70,6 +70,19 @@ class Match(NamedTuple):
     tau_index: Optional[torch.Tensor]  # int32: its index on the grid, the smallest one (``taus`` given)
     phase: torch.Tensor                # arg of the correlation there
     corr: Optional[torch.Tensor]       # [.., B, max(n_tau, 1), 2] normalised correlation over the whole grid (``corr=True``)
+
+
+class BankMatch(NamedTuple):
+    """Match of every predicted waveform against every template of a bank (:meth:`HeadDistribution.match_bank`): [n_z, B, G] per
+    (latent sample, task, template) and [n_z, B] per (latent sample, task); ``n_z = 1`` for ``of="mean"``."""
+    match: torch.Tensor                # [n_z, B, G] max over the constant phase and the time-shift grid
+    mismatch: torch.Tensor             # [n_z, B, G] 1 - match, formed in double
+    tau: Optional[torch.Tensor]        # [n_z, B, G] float64: the grid time that attains the match (``taus`` given)
+    tau_index: Optional[torch.Tensor]  # [n_z, B, G] int32: its index on the grid, the smallest one (``taus`` given)
+    phase: torch.Tensor                # [n_z, B, G] arg of the correlation there
+    best_index: torch.Tensor           # [n_z, B] int32: the template of the largest match, the smallest index
+    best_match: torch.Tensor           # [n_z, B] the match there
+    dot: Optional[torch.Tensor]        # [n_z, B, G, 2] float64: the unrounded correlation at the maximum (``dot=True``)
 
 
 class LogLike(NamedTuple):
@@ -260,6 +273,39 @@ class HeadDistribution(Independent):
         return Match(m.overlap.view(lead), m.match.view(lead), m.mismatch.view(lead), tau,
                      m.tau_index.view(lead) if taus is not None else None, m.phase.view(lead),
                      m.corr.view(*lead, *m.corr.shape[1:]) if corr else None)
+
+    def match_bank(self, bank, weights=None, freqs=None, taus=None, of="samples", dot=False) -> BankMatch:
+        """The match of every predicted waveform against every template of ``bank`` [G, T, 2] = (amplitude, phase) -> :class:`BankMatch`:
+        which template a prediction falls on (``best_index``, ``best_match``) and, with the predictions themselves as the bank,
+        which waveforms are distinguishable at all.  Every match is maximised over the constant phase and the grid ``taus = (tau0,
+        dtau, n_tau)`` as in :meth:`match`, in the same double arithmetic.  The bank is shared by the tasks, so ``weights`` and
+        ``freqs`` are [T] and the prediction must sit on one grid: padded targets (``n_trgt``) are refused.  ``of="samples"``: on the
+        raw decoder output, [n_z, B, G] (``base_dist`` is left alone); ``of="mean"``: the mixture-mean amplitude and phase, [1, B, G].
+        ``dot=True`` adds the unrounded complex correlation at the maximum.  One ``npf_waveform_match_bank`` call (the rotation by
+        the shift once per row, the contraction on the double-precision matrix instruction); inference only, no host sync, so a
+        ``query`` and its ``match_bank`` can be captured in one graph (call once at the sizes before capturing: the workspace is
+        allocated then)."""
+        if self._y_dim != 2:
+            raise ValueError(f"match_bank needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        if self._n_trgt is not None:
+            raise ValueError("match_bank: the prediction carries n_trgt (padded targets), but a bank needs one shared grid: every "
+                             "task must own all T points")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_match_bank_args((rows, T, ld), bank, weights, freqs, taus)
+        if of == "samples":
+            h = self._suff.detach().reshape(rows, T, ld)
+        else:
+            h = FN.mixture_summary(self._suff, n_z, self._y_dim, self._homosk)[0]
+        want = ("match", "mismatch", "phase", "best_index", "best_match") + (("tau_index",) if taus is not None else ())
+        m = FN.waveform_match_bank(h, bank, weights, freqs, taus, want=want, dot=dot)
+        lead, G = (rows // B, B), bank.shape[0]
+        tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(*lead, G) if taus is not None else None
+        return BankMatch(m.match.view(*lead, G), m.mismatch.view(*lead, G), tau,
+                         m.tau_index.view(*lead, G) if taus is not None else None, m.phase.view(*lead, G), m.best_index.view(lead),
+                         m.best_match.view(lead), m.dot.view(*lead, G, 2) if dot else None)
 
     def loglike(self, data, weights=None, freqs=None, taus=None, of="samples", series=False) -> LogLike:
         """The matched-filter log likelihood ratio of the complex detector data ``data`` [B, T, 2] = (Re d, Im d) with the predicted
