@@ -78,11 +78,12 @@ def ratios(got, ref):
 
 
 # ---- builders ----------------------------------------------------------------------------------------------------------------------
-def build(n_rows, n_bank, pts, n_tau, seed=0, h_ld=2, weighted=True):
+def build(n_rows, n_bank, pts, n_tau, seed=0, h_ld=2, weighted=True, pick=None, j_star=None):
     """One input set -> dict(h [n_rows, pts, h_ld], bank [n_bank, pts, 2], weights [pts] or None, freqs [pts], taus), fp32 CPU
     tensors.  The templates are chirps of distinct rates and phases with a falling amplitude; row r is template (5 r + 2) % n_bank
     shifted by the grid time of index (3 r + 1) % n_tau, with 5 % amplitude and 0.2 rad phase scatter, so ``best_index`` and
-    ``tau_index`` take many values.  Columns of ``h`` beyond the second hold noise: never read."""
+    ``tau_index`` take many values.  ``pick`` / ``j_star``: the template and the shift index of every row in the place of those
+    two rules (the random draws are the same).  Columns of ``h`` beyond the second hold noise: never read."""
     g = torch.Generator().manual_seed(7919 * seed + 13)
     x = torch.linspace(0.0, 1.0, pts, dtype=torch.float64) if pts > 1 else torch.zeros(1, dtype=torch.float64)
     f = (20.0 + 492.0 * x).float()
@@ -91,11 +92,11 @@ def build(n_rows, n_bank, pts, n_tau, seed=0, h_ld=2, weighted=True):
     k = torch.arange(n_bank, dtype=torch.float64).view(n_bank, 1)
     phase = (6.0 + 2.5 * k) * x.view(1, pts) ** 2 + 0.9 * k + 0.3 * torch.randn(n_bank, pts, generator=g, dtype=torch.float64)
     bank = torch.stack([amp, phase], -1).float()
-    pick = (5 * torch.arange(n_rows) + 2) % n_bank
+    pick = (5 * torch.arange(n_rows) + 2) % n_bank if pick is None else torch.as_tensor(pick, dtype=torch.long)
     ra = bank[pick, :, 0].double() * (1.0 + 0.05 * torch.randn(n_rows, pts, generator=g, dtype=torch.float64)).abs()
     rp = bank[pick, :, 1].double() + 0.2 * torch.randn(n_rows, pts, generator=g, dtype=torch.float64)
     if taus is not None:
-        j = (3 * torch.arange(n_rows) + 1) % n_tau
+        j = (3 * torch.arange(n_rows) + 1) % n_tau if j_star is None else torch.as_tensor(j_star, dtype=torch.long)
         rp = rp - TWO_PI * f.double().view(1, pts) * (taus[0] + j.double() * taus[1]).view(n_rows, 1)
     h = torch.randn(n_rows, pts, h_ld, generator=g)
     h[..., 0], h[..., 1] = ra.float(), rp.float()
