@@ -181,6 +181,16 @@ typedef struct npf_program {
  * LDS.  Replaces the reference functions listed at the top of this file. */
 int npf_chain_run(const npf_program_t *prog, void *stream);
 
+/* The kernel instance npf_chain_run launches for a program (host code only, nothing is launched):
+ * one of the values below, or NPF_EINVAL for a program npf_chain_run rejects. */
+#define NPF_CHAIN_BF16 1    /* bf16 weight images (reserved[2] == 1): <16 blocks, 4 waves>, four-slot ring     */
+#define NPF_CHAIN_EXTRA 2   /* a LayerNorm op: <16, 4> with the LayerNorm code, generic slab loop only          */
+#define NPF_CHAIN_WIDE 3    /* a layer side or PT operand above 256 features: <32, 4>, generic slab loop only   */
+#define NPF_CHAIN_PAIRED 4  /* reserved[1] == 2: <16, 8>, 128-point workgroups, three-slot ring, 256 -> 256     */
+#define NPF_CHAIN_N128 5    /* more 128 -> 128 than 256 -> 256 layers: <16, 4> with the 128 -> 128 pipeline     */
+#define NPF_CHAIN_DEFAULT 6 /* <16, 4> with the 256 -> 256 pipeline                                             */
+int npf_chain_instance(const npf_program_t *prog);
+
 /* ---- weight/bias gradients -------------------------------------------------------- */
 /* One job: dW[n][k] (+)= sum_p dZ[n][p] * A[k][p] and db[n] (+)= sum_p dZ[n][p], where dZ and
  * A are PT32 tensors with roundup(N,32) / roundup(K,32) features over the same points.

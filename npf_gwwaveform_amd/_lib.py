@@ -26,6 +26,8 @@ OP_END, OP_LOAD_PT, OP_STORE_PT, OP_LOAD_ROWS, OP_STORE_ROWS, OP_LINEAR, OP_SOFT
 # weight modes (enum npf_wmode)
 W_ROWMAJOR, W_PT_ROWS, W_PT_COLS = range(3)
 F_RELU, F_ADD_PT, F_MASK_PT, F_ADD_RM, F_P16, F_MASK_BITS, F_STORE_IN, F_STORE_P16, F_STORE_BITS = 1, 2, 4, 8, 16, 32, 64, 128, 256
+# kernel instances (npf_chain_instance)
+CHAIN_BF16, CHAIN_EXTRA, CHAIN_WIDE, CHAIN_PAIRED, CHAIN_N128, CHAIN_DEFAULT = range(1, 7)
 
 
 class NpfOp(C.Structure):
@@ -102,6 +104,7 @@ assert C.sizeof(NpfOp) == 80 and C.sizeof(NpfProgram) == 32 + 80 * NPF_MAX_OPS a
 _i32, _i64, _p = C.c_int32, C.c_int64, C.c_void_p
 SIGNATURES = {
     "npf_chain_run": (C.c_int, [C.POINTER(NpfProgram), _p]),
+    "npf_chain_instance": (C.c_int, [C.POINTER(NpfProgram)]),
     "npf_wgrad_run": (C.c_int, [C.POINTER(NpfWgradJob), _i32, _i32, _i32, _p, _i64, _p]),
     "npf_wgrad_partials_bytes": (_i64, [C.POINTER(NpfWgradJob), _i32, _i32, _i32]),
     "npf_gauss_head_fwd": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p]),

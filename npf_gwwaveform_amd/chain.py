@@ -50,6 +50,7 @@ def profile_end(ev0: Optional[torch.cuda.Event], name: str, flops: int, nbytes: 
 # inputs, saved tensors by (step, role), outputs, bf16) and ("bwd", chain, incoming gradients, buffers by (step, role), wgrad
 # jobs, bf16) -- so that a test can check each step against the kernel's OWN stored inputs (tests/teacher.py)
 TRACE = None
+LAUNCHED = None  # tests set this to a list: every launch then leaves (Program, kernel instance) -- see Program.instance
 DEBUG_ABLATE = 0  # development only: chain_kernel ablation bits (tools/microbench.py)
 # tests / tools: 1 = 64-point workgroups, 2 = 128-point (paired) workgroups, 0 = the library's choice
 FORCE_WG = int(os.environ.get("NPF_FORCE_WG", "0"))
@@ -409,9 +410,7 @@ class Program:
             lines.append(f"  {names.get(o.op, o.op):12s} i0={o.i0:4d} i1={o.i1:4d} i2={o.i2} i4={o.i4} {fl}")
         return "\n".join(lines)
 
-    def _launch(self) -> None:
-        if DUMP_PROGRAMS:
-            print(self.describe(), file=sys.stderr)
+    def _c_program(self) -> "L.NpfProgram":
         prog = L.NpfProgram()
         prog.n_ops = len(self.ops)
         prog.n_tasks, prog.pts_per_task, prog.tiles_per_task = self.n_tasks, self.pts, tiles_of(self.pts)
@@ -421,6 +420,19 @@ class Program:
         prog.reserved[2] = int(self.bf16)
         for i, o in enumerate(self.ops):
             prog.ops[i] = o
+        return prog
+
+    def instance(self) -> int:
+        """The kernel instance ``launch()`` runs this program on (``L.CHAIN_*``, ``npf_chain_instance``; host code only);
+        -1 for a program the library rejects."""
+        return L.load().npf_chain_instance(C.byref(self._c_program()))
+
+    def _launch(self) -> None:
+        if DUMP_PROGRAMS:
+            print(self.describe(), file=sys.stderr)
+        prog = self._c_program()
+        if LAUNCHED is not None:
+            LAUNCHED.append((self, L.load().npf_chain_instance(C.byref(prog))))
         L.check(L.load().npf_chain_run(C.byref(prog), L.stream_ptr()), "npf_chain_run")
 
 

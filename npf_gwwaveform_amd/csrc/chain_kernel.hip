@@ -1716,22 +1716,23 @@ static int validate(const npf_program_t* g) {
 
 }  // namespace npf
 
-extern "C" int npf_chain_run(const npf_program_t* prog, void* stream) {
-  const int rc = npf::validate(prog);
-  if (rc != NPF_OK) return rc;
-  int n_ops = prog->n_ops;
+namespace npf {
+
+// The program without what follows its first NPF_OP_END.
+static npf_program_t trimmed(const npf_program_t* prog) {
+  npf_program_t g = *prog;
   for (int i = 0; i < prog->n_ops; ++i)
     if (prog->ops[i].op == NPF_OP_END) {
-      n_ops = i;
+      g.n_ops = i;
       break;
     }
-  npf_program_t g = *prog;
-  g.n_ops = n_ops;
-  auto grid_for = [&](int tiles_per_wg) -> long {
-    if (g.wg_per_task) return (long)g.n_tasks * ((g.tiles_per_task + tiles_per_wg - 1) / tiles_per_wg);
-    return ((long)g.n_tasks * g.tiles_per_task + tiles_per_wg - 1) / tiles_per_wg;
-  };
-  bool wide = false;
+  return g;
+}
+
+// Which instance of chain_kernel runs a (validated, trimmed) program: the one place that decides it.
+static int choose_instance(const npf_program_t& g) {
+  bool wide = false, extra = false;
+  int n256 = 0, n128 = 0;
   for (int i = 0; i < g.n_ops; ++i) {
     const npf_op_t& o = g.ops[i];
     const bool feat_op = o.op == NPF_OP_LOAD_PT || o.op == NPF_OP_STORE_PT || o.op == NPF_OP_ADD_PT ||
@@ -1740,17 +1741,6 @@ extern "C" int npf_chain_run(const npf_program_t* prog, void* stream) {
                          o.op == NPF_OP_LOAD_RM;
     if (o.op == NPF_OP_LINEAR && (o.i0 > 256 || o.i1 > 256)) wide = true;
     if (feat_op && o.i0 > 256) wide = true;
-  }
-  // 64-point workgroups (two per CU) are the default; the 128-point paired variant is kept as a
-  // tested option (reserved[1] == 2, NPF_FORCE_WG=2): it halves the slab traffic per point but
-  // its lock-step phases overlap slightly worse on MI355X (23.5 vs 23.9 M points/s on config 2).
-  const bool paired = !wide && g.reserved[1] == 2;
-  const long grid = grid_for(paired ? 4 : 2);
-  if (grid <= 0 || grid > 0x7fffffffL) return NPF_EINVAL;
-  bool extra = false;
-  int n256 = 0, n128 = 0;
-  for (int i = 0; i < g.n_ops; ++i) {
-    const npf_op_t& o = g.ops[i];
     extra |= o.op == NPF_OP_LAYERNORM || o.op == NPF_OP_LAYERNORM_BWD;
     if (o.op == NPF_OP_LINEAR) {
       n256 += o.i0 == 256 && o.i1 == 256;
@@ -1759,8 +1749,7 @@ extern "C" int npf_chain_run(const npf_program_t* prog, void* stream) {
   }
   if (extra && wide) return NPF_EINVAL;
   // reserved[2] == 1: every LINEAR of the program takes a bf16 weight image (npf_cast_bf16_weights)
-  const bool bf16 = g.reserved[2] == 1;
-  if (bf16) {
+  if (g.reserved[2] == 1) {
     if (extra || wide) return NPF_EINVAL;
     for (int i = 0; i < g.n_ops; ++i) {
       const npf_op_t& o = g.ops[i];
@@ -1768,25 +1757,63 @@ extern "C" int npf_chain_run(const npf_program_t* prog, void* stream) {
                                     (o.s0 & 3)))
         return NPF_EINVAL;
     }
-    // (a 128-point paired bf16 instance <16, 8, ..., true> -- half the slab DMA per MFMA -- was measured: bare 8-layer
-    // chain 2.27 vs 2.08 ms, config-3 step 15.7 vs 15.9 ms: no gain, not kept)
-    hipLaunchKernelGGL((npf::chain_kernel<16, 4, false, 8, 8, true>), dim3((unsigned)grid_for(2)), dim3(256), 0,
-                       (hipStream_t)stream, g);
-    NPF_CHECK_LAUNCH();
-    return NPF_OK;
+    return NPF_CHAIN_BF16;
   }
-  const dim3 b4(256), b8(512);
+  if (extra) return NPF_CHAIN_EXTRA;
+  if (wide) return NPF_CHAIN_WIDE;
+  // 64-point workgroups (two per CU) are the default; the 128-point paired variant is kept as a
+  // tested option (reserved[1] == 2, NPF_FORCE_WG=2): it halves the slab traffic per point but
+  // its lock-step phases overlap slightly worse on MI355X (23.5 vs 23.9 M points/s on config 2).
+  if (g.reserved[1] == 2) return NPF_CHAIN_PAIRED;
+  if (n128 > n256) return NPF_CHAIN_N128;
+  return NPF_CHAIN_DEFAULT;
+}
+
+}  // namespace npf
+
+extern "C" int npf_chain_instance(const npf_program_t* prog) {
+  const int rc = npf::validate(prog);
+  if (rc != NPF_OK) return rc;
+  const npf_program_t g = npf::trimmed(prog);
+  return npf::choose_instance(g);
+}
+
+extern "C" int npf_chain_run(const npf_program_t* prog, void* stream) {
+  const int rc = npf::validate(prog);
+  if (rc != NPF_OK) return rc;
+  const npf_program_t g = npf::trimmed(prog);
+  const int inst = npf::choose_instance(g);
+  if (inst < 0) return inst;
+  auto grid_for = [&](int tiles_per_wg) -> long {
+    if (g.wg_per_task) return (long)g.n_tasks * ((g.tiles_per_task + tiles_per_wg - 1) / tiles_per_wg);
+    return ((long)g.n_tasks * g.tiles_per_task + tiles_per_wg - 1) / tiles_per_wg;
+  };
+  const long grid = grid_for(inst == NPF_CHAIN_PAIRED ? 4 : 2);
+  if (grid <= 0 || grid > 0x7fffffffL) return NPF_EINVAL;
+  const dim3 gd((unsigned)grid), b4(256), b8(512);
   const hipStream_t st = (hipStream_t)stream;
-  if (extra)
-    hipLaunchKernelGGL((npf::chain_kernel<16, 4, true, 0, 0, false>), dim3((unsigned)grid_for(2)), b4, 0, st, g);
-  else if (wide)
-    hipLaunchKernelGGL((npf::chain_kernel<32, 4, false, 0, 0, false>), dim3((unsigned)grid), b4, 0, st, g);
-  else if (paired)
-    hipLaunchKernelGGL((npf::chain_kernel<16, 8, false, 16, 8, false>), dim3((unsigned)grid), b8, 0, st, g);
-  else if (n128 > n256)
-    hipLaunchKernelGGL((npf::chain_kernel<16, 4, false, 8, 4, false>), dim3((unsigned)grid), b4, 0, st, g);
-  else
-    hipLaunchKernelGGL((npf::chain_kernel<16, 4, false, 16, 8, false>), dim3((unsigned)grid), b4, 0, st, g);
+  switch (inst) {
+    case NPF_CHAIN_BF16:
+      // (a 128-point paired bf16 instance <16, 8, ..., true> -- half the slab DMA per MFMA -- was measured: bare 8-layer
+      // chain 2.27 vs 2.08 ms, config-3 step 15.7 vs 15.9 ms: no gain, not kept)
+      hipLaunchKernelGGL((npf::chain_kernel<16, 4, false, 8, 8, true>), gd, b4, 0, st, g);
+      break;
+    case NPF_CHAIN_EXTRA:
+      hipLaunchKernelGGL((npf::chain_kernel<16, 4, true, 0, 0, false>), gd, b4, 0, st, g);
+      break;
+    case NPF_CHAIN_WIDE:
+      hipLaunchKernelGGL((npf::chain_kernel<32, 4, false, 0, 0, false>), gd, b4, 0, st, g);
+      break;
+    case NPF_CHAIN_PAIRED:
+      hipLaunchKernelGGL((npf::chain_kernel<16, 8, false, 16, 8, false>), gd, b8, 0, st, g);
+      break;
+    case NPF_CHAIN_N128:
+      hipLaunchKernelGGL((npf::chain_kernel<16, 4, false, 8, 4, false>), gd, b4, 0, st, g);
+      break;
+    default:
+      hipLaunchKernelGGL((npf::chain_kernel<16, 4, false, 16, 8, false>), gd, b4, 0, st, g);
+      break;
+  }
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }
