@@ -888,6 +888,65 @@ int npf_waveform_loglike_net(const float *h, int32_t h_ld, const float *d, const
                              double *series, double *lnl_mix, double *lnl_max_mix, double *hh_det, double *snr_det, double *dd_det,
                              void *workspace, void *stream);
 
+/* ---- sky-grid network likelihood (csrc/waveform_sky_kernels.hip; no reference counterpart)
+ * The coherent likelihood of npf_waveform_loglike_net at every pixel of ONE sky grid shared by the tasks, and its marginal over the
+ * pixels.  h, h_ld, d[n_tasks][D][pts][2], wgt ([D][pts] or [n_tasks][D][pts], NULL: ones), wgt_rows, n_valid, n_rows, n_tasks,
+ * n_det = D (1 <= D <= NPF_NET_MAX_DET), pts, tau0, dtau, n_tau, the rows r = s * n_tasks + b: as in npf_waveform_loglike_net.  A
+ * point is LIVE FOR DETECTOR k exactly as there (t < n_valid[b] and 0 < w_{k,t} < +inf); a point that is not live contributes an exact
+ * zero, chosen by a select and not a multiply, and nothing else of it is read in h, d or wgt (NaN included).
+ *   freq[pts]               fp32, ONE row shared by all tasks (the pixel operand is shared): required, freq_rows must be 1, read at
+ *                           every t < pts.  PRECONDITION: every entry is finite (the host does not read it).
+ *   resp[n_pix][D][2]       DOUBLE, DEVICE data: C_{p,k} = (Re, Im), the response of detector k to pixel p
+ *   delay[n_pix][D]         DOUBLE, DEVICE data: Delta_{p,k} in seconds, either sign, not tied to the grid; NULL: zeros
+ *   log_prior[n_pix]        DOUBLE, DEVICE data: the log prior MASS of every pixel; NULL: uniform, -ln n_pix each
+ * with 1 <= n_pix = P <= NPF_SKY_MAX_PIX.  The grid is shared by the tasks.  The host reads none of the three: all may be overwritten
+ * in place between the replays of a captured graph.  A pixel is LIVE if its log_prior is finite; a dead pixel gets no mass and -inf /
+ * 0 outputs, nothing of its resp or delay is read (NaN included), and nothing of it reaches another pixel.
+ * Everything in double, from fp32 inputs widened exactly; n = max(n_tau, 1), n_tau == 0 is the one candidate tau = 0 (the delays
+ * still enter):
+ *   K_{j,p}[r] = sum_k sum_t [w_{k,t} A_t e^{i phi_t} conj(d_{k,t}) e^{i 2 pi f_t tau_j}] [C_{p,k} e^{i 2 pi f_t Delta_{p,k}}]
+ *   hh_k[r]   = sum_t w_{k,t} A_t^2                     HH_p[r] = sum_k |C_{p,k}|^2 hh_k[r]       (k ascending)
+ *   x_{j,p}   = |K_{j,p}|                               L_{j,p} = ln I0(x_{j,p}) - HH_p / 2       (ln I0 of npf_waveform_loglike)
+ *   u_p       = log_prior_p + logsumexp_j L_{j,p} - ln n                        (-inf for a dead pixel)
+ *   lnl_sky[r]   = logsumexp_p u_p                      (no live pixel: -inf)
+ *   pix_index[r] = the smallest p attaining max_p u_p   (no live pixel: 0)
+ *   tau_index[r] = the smallest j attaining max_j x_{j,p*},  snr[r] = x_{j*,p*} / sqrt(HH_{p*})   (0 where HH_{p*} == 0), p* = pix_index
+ *                  (p* dead, which needs every pixel dead: tau_index = 0, snr = 0)
+ *   post[r][p]   = u_p - lnl_sky[r]                     (-inf at dead pixels, everywhere when none is live)
+ *   snr_map[r][p] = max_j x_{j,p} / sqrt(HH_p)          (0 where HH_p == 0 or the pixel is dead)
+ *   lnl_sky_mix[b] = log-mean-exp over the latent samples of lnl_sky
+ *   post_mix[b][p] = logmeanexp_s u_p[s, b] - lnl_sky_mix[b]
+ * A pixel with HH_p == 0 has Lambda = 1, so u_p = log_prior_p, by the formulas.  The prior is not normalised by the kernel.  The
+ * log-sum-exp over j is carried chunk by chunk with a running maximum.  A NaN at a live point of row r reaches row r's outputs and its
+ * task's mixtures only.
+ * The work is one complex GEMM with M = rows x n_tau, N = P, K = D x pts: the first bracket depends on (row, j) only, the second on
+ * the pixel only, and the detectors fold into the contraction axis, so the sum over k stays inside the modulus.  Launch 1 writes the
+ * operand panels in the fragment order of npf_waveform_match_bank (K axis: detector ascending, then point ascending, every detector's
+ * points padded to a multiple of 4 and rows / pixels to whole tiles of 16, all with exact zeros), the step e^{i 2 pi f dtau} and the
+ * start of every chunk of NPF_SKY_JC shifts once over t, and hh_k in a fixed order.  Launch 2: one wavefront per (16 rows, 16 pixels)
+ * on v_mfma_f64_16x16x4_f64; per chunk the 2 NPF_SKY_JC accumulator tiles, ln I0 on them, the running log-sum-exp over j and the
+ * running max x with its first j stay in registers: nothing of size [n_rows][n_pix][n_tau] is written.  Launch 3: one workgroup per
+ * task over its n_z rows in order; the sum over the pixels is taken in 2^-62 fixed point on integer accumulators, so lnl_sky and post
+ * do not depend on the order of the pixels (error <= P 2^-62 of the largest term).  No atomics: a second call on the same inputs gives
+ * the same bits, and the value at (row, pixel) does not depend on the tile, wavefront or workgroup that computed it.  The host reads
+ * no device data: the call sits in a captured graph.
+ * Outputs, all DOUBLE but the two int32 indices (each may be NULL, at least one must be given; every requested element is written):
+ * lnl_sky / pix_index / tau_index / snr [n_rows], lnl_sky_mix [n_tasks], post / snr_map [n_rows][n_pix], post_mix [n_tasks][n_pix].
+ * workspace: npf_waveform_loglike_sky_workspace_bytes(n_rows, n_det, pts, n_pix, n_tau) bytes of device memory, 8-byte aligned (-1
+ * for sizes the call refuses).  NPF_SKY_MAX_PIX = 65536 keeps that count in int64: the largest term, the row panel, is at most 2^24
+ * rows x 8 detectors x 2^31 points x 16 bytes = 2^62.
+ * Status: NPF_EINVAL (nothing launched) for everything npf_waveform_loglike_net refuses, freq_rows != 1, a NULL freq or resp, n_pix
+ * outside [1, NPF_SKY_MAX_PIX], all outputs NULL. */
+#define NPF_SKY_JC 8
+#define NPF_SKY_MAX_PIX 65536
+int64_t npf_waveform_loglike_sky_workspace_bytes(int32_t n_rows, int32_t n_det, int32_t pts, int32_t n_pix, int32_t n_tau);
+int npf_waveform_loglike_sky(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                             int32_t freq_rows, const int32_t *n_valid, const double *resp, const double *delay,
+                             const double *log_prior, int32_t n_rows, int32_t n_tasks, int32_t n_det, int32_t pts, int32_t n_pix,
+                             double tau0, double dtau, int32_t n_tau, double *lnl_sky, int32_t *pix_index, int32_t *tau_index,
+                             double *snr, double *lnl_sky_mix, double *post, double *snr_map, double *post_mix, void *workspace,
+                             void *stream);
+
 /* ---- distance-marginalised likelihood (csrc/waveform_dist_kernels.hip; no reference counterpart)
  * The predicted waveform is a template at a reference distance d_ref; at luminosity distance d it is a h with the amplitude scale
  * a = d_ref / d.  npf_waveform_loglike_dist marginalises the likelihood of npf_waveform_loglike over a grid of scales as well,

@@ -768,6 +768,120 @@ def waveform_loglike_network(h: torch.Tensor, data: torch.Tensor, response: torc
     return WaveformLogLikeNetwork(*(out[name] for name in LOGLIKE_NET_NAMES), ser)
 
 
+# ---- sky-grid network likelihood (csrc/waveform_sky_kernels.hip) --------------
+SKY_MAX_PIX = 65536  # NPF_SKY_MAX_PIX
+SKY_JC = 8           # NPF_SKY_JC: time shifts per chunk of the correlation launch
+LOGLIKE_SKY_NAMES = ("lnl_sky", "pix_index", "tau_index", "snr", "lnl_sky_mix")
+
+
+class WaveformLogLikeSky(NamedTuple):
+    """What :func:`waveform_loglike_sky` returns (float64 but the two indices); the entries that were not asked for are ``None``."""
+    lnl_sky: Optional[torch.Tensor]      # [R] phase, time and sky position marginalised
+    pix_index: Optional[torch.Tensor]    # [R] int32: the pixel of the largest evidence, the smallest index
+    tau_index: Optional[torch.Tensor]    # [R] int32: the grid time of the largest |K_j| at that pixel
+    snr: Optional[torch.Tensor]          # [R] max_j |K_j| / sqrt(HH) at that pixel
+    lnl_sky_mix: Optional[torch.Tensor]  # [B] lnl_sky marginalised over the latent samples
+    post: Optional[torch.Tensor]         # [R, P] log posterior mass of every pixel (``posterior=True``)
+    post_mix: Optional[torch.Tensor]     # [B, P] the same with the latent samples marginalised (``posterior=True``)
+    snr_map: Optional[torch.Tensor]      # [R, P] max_j |K_j| / sqrt(HH) of every pixel (``snr_map=True``)
+
+
+def check_loglike_sky_args(h_shape, data, response, delays, log_prior=None, weights=None, freqs=None, taus=None):
+    """The shapes, dtypes and host values of a :func:`waveform_loglike_sky` call -> ``(R, T, h_ld, B, D, P, wgt_rows, tau0, dtau,
+    n_tau)``; ``ValueError`` for anything that does not fit.  Reads shapes and dtypes only, so it runs on tensors of any device:
+    ``h_shape`` = [R, T, >= 2], ``data`` [B, D, T, 2] with ``1 <= D <= NET_MAX_DET`` and ``R % B == 0``, ``response`` float64
+    [P, D, 2] with ``1 <= P <= SKY_MAX_PIX``, ``delays`` float64 [P, D], ``log_prior`` ``None`` or float64 [P], ``weights``
+    ``None``, [D, T] or [B, D, T], ``freqs`` [T] -- required, and one row: the sky grid is shared by the tasks, so [B, T] is refused
+    -- and ``taus`` as in :func:`check_match_args`."""
+    h_shape = tuple(h_shape)
+    if len(h_shape) != 3 or h_shape[2] < 2 or h_shape[0] < 1 or h_shape[1] < 1:
+        raise ValueError(f"h must have shape [R, T, >= 2] (amplitude, phase first), got {list(h_shape)}")
+    R, T, ld = h_shape
+    shape_of = lambda t: (f"{list(t.shape)} of {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__)  # noqa: E731
+    if not isinstance(data, torch.Tensor) or data.dim() != 4 or data.shape[0] < 1 or tuple(data.shape[2:]) != (T, 2):
+        raise ValueError(f"data = (Re, Im) per detector must have shape [B, D, T={T}, 2], got {shape_of(data)}")
+    B, D = data.shape[0], data.shape[1]
+    if not 1 <= D <= NET_MAX_DET:
+        raise ValueError(f"data holds {D} detectors: 1 <= D <= {NET_MAX_DET}")
+    if R % B != 0:
+        raise ValueError(f"h holds {R} rows, data {B} tasks: R % B != 0 (row k * B + b is latent sample k of task b)")
+    if not isinstance(response, torch.Tensor) or response.dim() != 3 or tuple(response.shape[1:]) != (D, 2) \
+            or response.dtype != torch.float64:
+        raise ValueError(f"response = (Re C, Im C) per pixel must be a float64 tensor of shape [P, D={D}, 2], got {shape_of(response)}")
+    P = response.shape[0]
+    if not 1 <= P <= SKY_MAX_PIX:
+        raise ValueError(f"response holds {P} pixels: 1 <= P <= {SKY_MAX_PIX}")
+    if not isinstance(delays, torch.Tensor) or tuple(delays.shape) != (P, D) or delays.dtype != torch.float64:
+        raise ValueError(f"delays (seconds) per pixel must be a float64 tensor of shape [P={P}, D={D}], got {shape_of(delays)}")
+    if log_prior is not None and (not isinstance(log_prior, torch.Tensor) or tuple(log_prior.shape) != (P,)
+                                  or log_prior.dtype != torch.float64):
+        raise ValueError(f"log_prior must be None or a float64 tensor of shape [P={P}], got {shape_of(log_prior)}")
+    if weights is not None and (not isinstance(weights, torch.Tensor) or tuple(weights.shape) not in ((D, T), (B, D, T))):
+        raise ValueError(f"weights must be None or a tensor of shape [D={D}, T={T}] or [B={B}, D={D}, T={T}], got {shape_of(weights)}")
+    if freqs is None:
+        raise ValueError("freqs is required: the delays of a pixel enter as the phase 2 pi f delay")
+    if not isinstance(freqs, torch.Tensor) or tuple(freqs.shape) != (T,):
+        raise ValueError(f"freqs must be a tensor of shape [T={T}] (one grid: the sky grid is shared by the tasks), got {shape_of(freqs)}")
+    wgt_rows = 1 if weights is None or weights.dim() == 2 else B
+    taus = check_taus(taus, True)
+    tau0, dtau, n_tau = taus if taus is not None else (0.0, 0.0, 0)
+    return R, T, ld, B, D, P, wgt_rows, tau0, dtau, n_tau
+
+
+def waveform_loglike_sky(h: torch.Tensor, data: torch.Tensor, response: torch.Tensor, delays: torch.Tensor,
+                         log_prior: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                         freqs: Optional[torch.Tensor] = None, taus=None, n_valid: Optional[torch.Tensor] = None,
+                         want=LOGLIKE_SKY_NAMES, posterior: bool = False, snr_map: bool = False) -> WaveformLogLikeSky:
+    """The coherent network likelihood of :func:`waveform_loglike_network` at every pixel of ONE sky grid shared by the tasks, and
+    its marginal over the pixels.  ``response`` [P, D, 2] = (Re C, Im C), ``delays`` [P, D] (seconds, either sign, not tied to the
+    grid) and ``log_prior`` [P] (the log prior MASS of every pixel; ``None``: uniform, ``-ln P`` each; not normalised by the
+    kernel) are float64 DEVICE tensors the host never reads, so a captured graph sees what they hold at replay.  A pixel whose
+    ``log_prior`` is not finite is dead: no mass, ``-inf`` in ``post``, 0 in ``snr_map``, and nothing of its response or delays
+    is used.  With ``K_{j,p} = sum_k C_{p,k} kappa_{k,j}(delay_{p,k})`` and ``HH_p = sum_k |C_{p,k}|^2 hh_k``:
+    ``u_p = log_prior_p + logsumexp_j (ln I0(|K_{j,p}|) - HH_p / 2) - ln n_tau``, ``lnl_sky = logsumexp_p u_p``, ``pix_index``
+    the smallest pixel of the largest ``u_p``, ``tau_index`` and ``snr`` as in the network call at that pixel, ``lnl_sky_mix``
+    [B] the log-mean-exp of ``lnl_sky`` over the ``R / B`` latent samples; ``posterior=True`` adds ``post`` [R, P] = ``u_p -
+    lnl_sky`` (the sky map) and ``post_mix`` [B, P], ``snr_map=True`` the best SNR of every pixel [R, P].
+    ``include/npf_hip.h`` has the contract and the edge cases.  ``data``, ``weights``, ``taus``, ``n_valid``: as in
+    :func:`waveform_loglike_network`.  ``freqs`` [T] is required, shared by all tasks, and must be finite.  ``want``: names out of
+    ``LOGLIKE_SKY_NAMES``.  ``npf_waveform_loglike_sky``: one complex GEMM with M = R n_tau, N = P, K = D T on the double-precision
+    matrix instruction -- the rotation by ``tau_j`` is done once per row, not once per pixel -- in three launches; inference only,
+    no host sync, deterministic; the workspace is the one of :func:`waveform_match`.
+    Out of scope: antenna patterns and delays from (ra, dec, psi, iota), which come from the caller's GW library; a sky grid per
+    task; gradients; distance marginalised jointly with the sky; adaptive or hierarchical pixel refinement."""
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or any(w not in LOGLIKE_SKY_NAMES for w in want):
+        raise ValueError(f"want must be a tuple / list of names out of {LOGLIKE_SKY_NAMES}, got {want!r}")
+    want = tuple(want)
+    R, T, ld, B, D, P, wgt_rows, tau0, dtau, n_tau = check_loglike_sky_args(getattr(h, "shape", ()), data, response, delays, log_prior,
+                                                                            weights, freqs, taus)
+    if not want and not posterior and not snr_map:
+        raise ValueError(f"want must name at least one of {LOGLIKE_SKY_NAMES} (or posterior=True / snr_map=True)")
+    for t in (h, data, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    for t, what in ((response, "response"), (delays, "delays"), (log_prior, "log_prior")):
+        if t is not None and (not t.is_cuda or t.device != h.device):
+            raise ValueError(f"{what} must live on the device of h ({h.device}), got {t.device}: the kernel reads it there")
+    h, data, freqs = h.detach().contiguous(), data.detach().contiguous(), freqs.detach().contiguous()
+    response, delays = response.detach().contiguous(), delays.detach().contiguous()
+    log_prior = log_prior.detach().contiguous() if log_prior is not None else None
+    weights = weights.detach().contiguous() if weights is not None else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    lib = L.load()
+    ws = _match_workspace(h.device, int(lib.npf_waveform_loglike_sky_workspace_bytes(R, D, T, P, n_tau)))
+    out = {name: (torch.empty((B if name == "lnl_sky_mix" else R,), dtype=torch.int32 if name.endswith("index") else torch.float64,
+                              device=h.device) if name in want else None) for name in LOGLIKE_SKY_NAMES}
+    new = lambda rows: torch.empty((rows, P), dtype=torch.float64, device=h.device)  # noqa: E731
+    post, post_mix = (new(R), new(B)) if posterior else (None, None)
+    smap = new(R) if snr_map else None
+    dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    L.check(lib.npf_waveform_loglike_sky(L.ptr(h), ld, L.ptr(data), L.ptr(weights), wgt_rows, L.ptr(freqs), 1,
+                                         _iptr(nv) if nv is not None else None, dptr(response), dptr(delays), dptr(log_prior), R, B, D,
+                                         T, P, tau0, dtau, n_tau, *(dptr(out[name]) for name in LOGLIKE_SKY_NAMES), dptr(post),
+                                         dptr(smap), dptr(post_mix), ws.data_ptr(), L.stream_ptr()), "npf_waveform_loglike_sky")
+    return WaveformLogLikeSky(*(out[name] for name in LOGLIKE_SKY_NAMES), post, post_mix, smap)
+
+
 # ---- differentiable likelihoods (csrc/waveform_grad_kernels.hip) --------------
 class WaveformLnl(NamedTuple):
     """What :func:`waveform_lnl` / :func:`waveform_lnl_network` return: the four likelihoods (float64, differentiable with respect to

@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlat
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "BankMatch", "LogLike", "NetworkLogLike", "DistanceLogLike",
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "BankMatch", "LogLike", "NetworkLogLike", "SkyLogLike", "DistanceLogLike",
            "NetworkDistanceLogLike", "Reweighted", "bootstrap_weights",
            "kfold_weights"]
 
@@ -120,6 +120,20 @@ class NetworkLogLike(NamedTuple):
     snr_det: torch.Tensor              # [.., B, D] |<d_k|h>_k| / sqrt(<h|h>_k) at the network's grid time
     optimal_snr_det: torch.Tensor      # [.., B, D] |C_k| sqrt(<h|h>_k)
     dd_det: torch.Tensor               # [B, D] <d_k|d_k>
+
+
+class SkyLogLike(NamedTuple):
+    """Sky-grid network likelihood (:meth:`HeadDistribution.loglike_sky`), float64 (but the indices).  Per (latent sample, task):
+    [n_z, B] for ``of="samples"``, [1, B] for ``of="mean"``; per task: [B]; per pixel: a last axis of ``P``."""
+    lnl: torch.Tensor                  # [B] lnl_sky marginalised over the latent samples: log-mean-exp
+    lnl_sky: torch.Tensor              # ln Lambda marginalised over the shared phase, the grid times and the sky pixels (prior as given)
+    pix_index: torch.Tensor            # int32: the pixel of the largest evidence, the smallest index
+    tau_index: Optional[torch.Tensor]  # int32: the grid time of the largest |K_j| at that pixel, the smallest one (``taus`` given)
+    tau: Optional[torch.Tensor]        # that grid time (``taus`` given)
+    snr: torch.Tensor                  # the network SNR at that pixel and grid time
+    post: Optional[torch.Tensor]       # [.., B, P] log posterior mass of every pixel: the sky map (``posterior=True``)
+    post_mix: Optional[torch.Tensor]   # [B, P] the same with the latent samples marginalised (``posterior=True``)
+    snr_map: Optional[torch.Tensor]    # [.., B, P] the best network SNR of every pixel (``snr_map=True``)
 
 
 class DistanceLogLike(NamedTuple):
@@ -439,6 +453,43 @@ class HeadDistribution(Independent):
                                                      n_valid=self._n_trgt, want=want, posterior=posterior)
             lead = (rows // B, B)
             return NetworkDistanceLogLike(*self._distance_fields(m, scales, lead), _as_network_loglike(m.base, taus, lead, response))
+
+    def loglike_sky(self, data, response, delays, log_prior=None, weights=None, freqs=None, taus=None, of="samples", posterior=True,
+                    snr_map=False) -> SkyLogLike:
+        """:meth:`loglike_network` at every pixel of a sky grid, marginalised over the pixels -> :class:`SkyLogLike`: the sky map
+        of an event under the predicted waveform in one call.  The grid is ONE grid shared by the tasks: ``response`` [P, D, 2] =
+        (Re C, Im C) and ``delays`` [P, D] (seconds) hold every detector's response and arrival delay at every pixel, ``log_prior``
+        [P] the log prior MASS of every pixel (``None``: uniform; not normalised here), all float64 device tensors the host never
+        reads; a pixel whose ``log_prior`` is not finite is dead (no mass, ``-inf`` in ``post``, 0 in ``snr_map``).  ``lnl_sky``
+        is the likelihood marginal over the coalescence phase, the grid of arrival times and the pixels, ``lnl`` [B] its
+        log-mean-exp over the latent samples; ``pix_index`` is the pixel of the largest evidence and ``tau_index`` / ``tau`` /
+        ``snr`` what :meth:`loglike_network` reports there.  ``posterior=True`` adds ``post`` (per latent sample) and
+        ``post_mix`` [B, P], the sky posterior with the model's own waveform uncertainty marginalised out; ``snr_map=True`` the
+        best SNR of every pixel.  ``freqs`` [T] is required, shared by all tasks (the pixel operand is), and must be finite.
+        ``data``, ``weights``, ``taus``, ``of``, padded targets: as in :meth:`loglike_network`.  One
+        ``npf_waveform_loglike_sky`` call: a complex GEMM with M = rows x n_tau, N = P, K = D T on the double-precision matrix
+        instruction, three launches in place of ``2 P``; inference only, no host sync, so a ``query`` and its ``loglike_sky`` can
+        be captured in one graph (call once at the sizes before capturing) and replayed after ``response`` / ``delays`` /
+        ``log_prior`` were overwritten in place.
+        Out of scope: antenna patterns and delays from (ra, dec, psi, iota), which come from the caller's GW library; a sky grid
+        per task; gradients; distance marginalised jointly with the sky; adaptive or hierarchical pixel refinement."""
+        if self._y_dim != 2:
+            raise ValueError(f"loglike_sky needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_loglike_sky_args((rows, T, ld), data, response, delays, log_prior, weights, freqs, taus)
+        with torch.no_grad():
+            h = self._waveform_rows(of, rows, ld)
+            m = FN.waveform_loglike_sky(h, data, response, delays, log_prior, weights, freqs, taus, n_valid=self._n_trgt,
+                                        posterior=posterior, snr_map=snr_map)
+            lead, P = (rows // B, B), response.shape[0]
+            tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
+            return SkyLogLike(m.lnl_sky_mix, m.lnl_sky.view(lead), m.pix_index.view(lead),
+                              m.tau_index.view(lead) if taus is not None else None, tau, m.snr.view(lead),
+                              m.post.view(*lead, P) if posterior else None, m.post_mix,
+                              m.snr_map.view(*lead, P) if snr_map else None)
 
     def _waveform_rows(self, of, rows, ld):
         """The (amplitude, phase) rows a likelihood is evaluated on: the raw decoder output or the mixture mean."""
