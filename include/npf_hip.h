@@ -918,7 +918,8 @@ int npf_waveform_loglike_net(const float *h, int32_t h_ld, const float *d, const
  *   post_mix[b][p] = logmeanexp_s u_p[s, b] - lnl_sky_mix[b]
  * A pixel with HH_p == 0 has Lambda = 1, so u_p = log_prior_p, by the formulas.  The prior is not normalised by the kernel.  The
  * log-sum-exp over j is carried chunk by chunk with a running maximum.  A NaN at a live point of row r reaches row r's outputs and its
- * task's mixtures only.
+ * task's mixtures only.  A NaN in the resp or delay of a LIVE pixel p makes K_{j,p} and HH_p NaN, so snr_map[r][p] and u_p, and with
+ * u_p lnl_sky[r] and lnl_sky_mix, are NaN in every row, while snr_map at every other pixel keeps its bits.
  * The work is one complex GEMM with M = rows x n_tau, N = P, K = D x pts: the first bracket depends on (row, j) only, the second on
  * the pixel only, and the detectors fold into the contraction axis, so the sum over k stays inside the modulus.  Launch 1 writes the
  * operand panels in the fragment order of npf_waveform_match_bank (K axis: detector ascending, then point ascending, every detector's
