@@ -1005,6 +1005,59 @@ int npf_waveform_loglike_net_dist(const float *h, int32_t h_ld, const float *d, 
                                   double *lnl_dist, int32_t *scale_index, double *scale_hat, double *lnl_amp_max, double *lnl_dist_mix,
                                   double *post, double *post_mix, void *workspace, void *stream);
 
+/* ---- sky and distance marginalised jointly (csrc/waveform_sky_kernels.hip; no reference counterpart)
+ * The likelihood of npf_waveform_loglike_sky at every pixel of the shared sky grid AND every scale of ONE scale grid shared by the
+ * tasks.  The arguments up to n_tau are those of npf_waveform_loglike_sky, under its rules (live points, live pixels, freq_rows == 1,
+ * the preconditions on freq); then
+ *   scales[n_a]            DOUBLE, DEVICE data: a_i
+ *   log_prior_scale[n_a]   DOUBLE, DEVICE data: ln pi_i, the log prior MASS of grid point i (quadrature weight included)
+ * with 1 <= n_a <= NPF_DIST_MAX_SCALES and the liveness rule of npf_waveform_loglike_dist (0 < a_i < +inf and ln pi_i finite; nothing
+ * else of a dead scale is used, NaN included).  The host reads neither.  With x_{p,j} = |K_{j,p}|, HH_p, n = max(n_tau, 1) and lp_p
+ * (NULL: -ln n_pix) of the sky call, x*_p = max_j x_{p,j}, all in double:
+ *   w_{p,i} = lp_p + ((ln pi_i + (ln I0(a_i x*_p) - a_i^2 HH_p / 2)) + (ln sum_j exp(ln I0(a_i x_{p,j}) - ln I0(a_i x*_p)) - ln n))
+ *             (dead p or dead i: -inf; every term of the sum <= 1)
+ *   lnl_vol[r]        = logsumexp_{p,i} w_{p,i}                                  (no live pixel or no live scale: -inf)
+ *   post_sky[r][p]    = logsumexp_i w_{p,i} - lnl_vol[r]   (= u_sky[p] - lnl_vol)     post_dist[r][i] = logsumexp_p w_{p,i} - lnl_vol[r]
+ *   post_joint[r][p][i] = w_{p,i} - lnl_vol[r]
+ *   pix_index[r]      = the smallest p attaining max_p u_sky[p]    scale_index[r] = the smallest i attaining max_i u_dist[i]
+ *   tau_index[r], snr[r] = what npf_waveform_loglike_sky reports at pixel pix_index;  scale_hat[r] = x* / HH there (0 where HH == 0)
+ *   dist_mean[r][p]   = sum_i (1 / a_i) exp(w_{p,i} - u_sky[p])                   (E[d / d_ref | pixel p])
+ *   dist_std[r][p]    = sqrt(sum_i (1 / a_i - dist_mean)^2 exp(w_{p,i} - u_sky[p]))   (a second pass about the mean)
+ *   lnl[b]            = logsumexp_s lnl_vol[s n_tasks + b] - ln n_z
+ *   post_sky_mix[b][p]  = logsumexp_s u_sky[s n_tasks + b][p] - ln n_z - lnl[b]      post_dist_mix[b][i]: the same of u_dist
+ * A dead pixel or scale gets -inf in every posterior and 0 in dist_mean / dist_std.  With no live pixel or no live scale lnl_vol is
+ * -inf, the indices are 0 and snr = scale_hat = 0.  A pixel with HH_p == 0 is treated as x = 0: w_{p,i} = lp_p + ln pi_i.  The priors
+ * are not normalised.  The posteriors are differences first -- with mm_p = max_i w, s_p = sum_i exp(w - mm_p), M = max w and total =
+ * sum_p exp(mm_p - M) s_p: post_sky = (mm_p - M) + (ln s_p - ln total), post_joint = (w - M) - ln total, post_dist likewise -- so each
+ * sums to one to rounding where w reaches 1e6.  Sums over the pixels (total, and sum_p exp(w_{p,i} - max_p w) of every scale) are
+ * taken in the 2^-62 fixed point of npf_waveform_loglike_sky on integer accumulators: they do not depend on the order of the pixels;
+ * sums over the scales run in ascending i.  A NaN in the resp or delay of a LIVE pixel makes that pixel's w NaN in every row: lnl_vol,
+ * lnl, post_* are NaN, while dist_mean / dist_std at every other pixel keep their bits.
+ * Launch 1: the prep launch of npf_waveform_loglike_sky.  Launch 2: its f64 MFMA correlation with an epilogue that stores x_{p,j} to
+ * the panel X[n_rows][n][pix_pad] (pix_pad = n_pix rounded up to 16; the 16 lanes of a C/D fragment row store one 128-byte line) and
+ * keeps max_j x, its first j and HH_p.  Launch 3: one wavefront per (row, 64 pixels, NPF_SKYD_SC scales), one pass over j, w to the
+ * panel W[n_rows][n_a][pix_pad].  Launch 4: one workgroup per task over its n_z rows in order.  No atomics, no host read: a second
+ * call gives the same bits and the call sits in a captured graph.
+ * Outputs, all DOUBLE but the three int32 indices (each may be NULL, at least one must be given; every requested element is written):
+ * lnl_vol / pix_index / scale_index / tau_index / snr / scale_hat [n_rows], lnl [n_tasks], post_sky / dist_mean / dist_std
+ * [n_rows][n_pix], post_dist [n_rows][n_a], post_joint [n_rows][n_pix][n_a], post_sky_mix [n_tasks][n_pix], post_dist_mix
+ * [n_tasks][n_a].
+ * workspace: npf_waveform_loglike_sky_dist_workspace_bytes(n_rows, n_det, pts, n_pix, n_tau, n_a) bytes of device memory, 8-byte
+ * aligned (-1 for sizes the call refuses and for a count that does not fit int64).
+ * Status: NPF_EINVAL (nothing launched) for everything npf_waveform_loglike_sky refuses, a NULL scales or log_prior_scale, n_a outside
+ * [1, NPF_DIST_MAX_SCALES], a workspace count beyond int64, all outputs NULL. */
+#define NPF_SKYD_SC 8
+int64_t npf_waveform_loglike_sky_dist_workspace_bytes(int32_t n_rows, int32_t n_det, int32_t pts, int32_t n_pix, int32_t n_tau,
+                                                      int32_t n_a);
+int npf_waveform_loglike_sky_dist(const float *h, int32_t h_ld, const float *d, const float *wgt, int32_t wgt_rows, const float *freq,
+                                  int32_t freq_rows, const int32_t *n_valid, const double *resp, const double *delay,
+                                  const double *log_prior, int32_t n_rows, int32_t n_tasks, int32_t n_det, int32_t pts, int32_t n_pix,
+                                  double tau0, double dtau, int32_t n_tau, const double *scales, const double *log_prior_scale,
+                                  int32_t n_a, double *lnl_vol, int32_t *pix_index, int32_t *scale_index, int32_t *tau_index,
+                                  double *snr, double *scale_hat, double *lnl, double *post_sky, double *post_dist, double *post_joint,
+                                  double *dist_mean, double *dist_std, double *post_sky_mix, double *post_dist_mix, void *workspace,
+                                  void *stream);
+
 /* ---- gradient of the matched-filter likelihoods with respect to the predicted waveform (csrc/waveform_grad_kernels.hip; no reference
  * counterpart).  npf_waveform_loglike_ex / npf_waveform_loglike_net_ex are npf_waveform_loglike / npf_waveform_loglike_net with one
  * more argument before workspace: every output of the parent comes from the parent's own launches and is BIT-EQUAL to a plain call,

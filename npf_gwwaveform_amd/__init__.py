@@ -11,7 +11,7 @@ from .datasplit import CntxtTrgtGetter, GetRandomIndcs, GetRangeIndcs, get_all_i
 from .evaluate import eval_loglike
 from .losses import CNPFLoss, ELBOLossLNPF, LightTailPareto, LogLikeLoss, MismatchLoss, NLLLossLNPF, SUMOLossLNPF
 from .neuralproc import (CNP, LNP, AttnCNP, AttnLNP, BankMatch, Conditioned, DistanceLogLike, HeadDistribution, LatentNeuralProcessFamily, Lnl, LogLike, Match,
-                         MultivariateNormalDiag, NetworkDistanceLogLike, NetworkLogLike, NeuralProcessFamily, Prediction, Reweighted, Score, SkyLogLike, bootstrap_weights, kfold_weights)
+                         MultivariateNormalDiag, NetworkDistanceLogLike, NetworkLogLike, NeuralProcessFamily, Prediction, Reweighted, Score, SkyDistanceLogLike, SkyLogLike, bootstrap_weights, kfold_weights)
 
 # north-star aliases: NPFModel / encode / aggregate / decode
 NPFModel = NeuralProcessFamily
@@ -39,5 +39,5 @@ __all__ = [
     "NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP", "NPFModel",
     "CNPFLoss", "ELBOLossLNPF", "NLLLossLNPF", "SUMOLossLNPF", "MismatchLoss", "LogLikeLoss", "LightTailPareto", "MultivariateNormalDiag", "encode", "aggregate", "decode",
     "CntxtTrgtGetter", "GetRandomIndcs", "GetRangeIndcs", "get_all_indcs", "set_compute_dtype", "eval_loglike", "HeadDistribution",
-    "Conditioned", "Prediction", "Score", "Match", "BankMatch", "LogLike", "Lnl", "NetworkLogLike", "SkyLogLike", "DistanceLogLike", "NetworkDistanceLogLike", "Reweighted", "KeyWeights", "TrainKeyWeights", "bootstrap_weights", "kfold_weights",
+    "Conditioned", "Prediction", "Score", "Match", "BankMatch", "LogLike", "Lnl", "NetworkLogLike", "SkyLogLike", "SkyDistanceLogLike", "DistanceLogLike", "NetworkDistanceLogLike", "Reweighted", "KeyWeights", "TrainKeyWeights", "bootstrap_weights", "kfold_weights",
 ]

@@ -178,6 +178,10 @@ SIGNATURES = {
     "npf_waveform_loglike_net_dist": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_double,
                                                 C.c_double, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _i32,
                                                 _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "npf_waveform_loglike_sky_dist_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "npf_waveform_loglike_sky_dist": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_double,
+                                                C.c_double, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                _p, _p]),
     "npf_waveform_loglike_saved_doubles": (_i64, [_i32]),
     "npf_waveform_loglike_ex": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, C.c_double, C.c_double, _i32,
                                           _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

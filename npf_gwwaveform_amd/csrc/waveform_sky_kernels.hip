@@ -447,3 +447,487 @@ extern "C" int npf_waveform_loglike_sky(const float* h, int32_t h_ld, const floa
   NPF_CHECK_LAUNCH();
   return NPF_OK;
 }
+
+// ---- sky and distance marginalised jointly ----------------------------------------------------------------------------------------
+// Sky and distance marginalised jointly (npf_waveform_loglike_sky_dist): the coherent likelihood of npf_waveform_loglike_sky at every
+// pixel p of the shared sky grid AND every amplitude scale a_i of a shared scale grid.  With x_{p,j} = |K_{j,p}|,
+// HH_p, n = max(n_tau, 1) and the pixel prior lp_p of the sky call, a_i and ln pi_i of the distance call:
+//   w_{p,i} = lp_p + ln pi_i + (logsumexp_j ln I0(a_i x_{p,j}) - ln n) - a_i^2 HH_p / 2        (-inf for a dead pixel or a dead scale)
+// and everything else is sums of exp(w) over p, over i or over both.  DOUBLE throughout.
+//
+// Launch 1: sky_prep_kernel of the sky call, as it is.
+// Launch 2 (skyd_corr_kernel): the f64 MFMA correlation of sky_corr_kernel, the same sky_chunk k loop and the same wavefront per (16
+// rows, 16 pixels).  Its epilogue takes no logarithm: x = |K| of every accumulator goes to the x panel, and the running max of x_j with
+// its first j stays in registers; at the end max x, j and HH_p go to the workspace with sky_corr_kernel's own arithmetic.
+//   x panel: X[r][j][pix_pad], the pixel fastest.  The C/D fragment has 16 pixels across lane & 15, so the 16 lanes of one fragment
+//   row store 16 consecutive doubles: one whole 128-byte line (pix_pad is a multiple of 16 and the panel starts on a 128-byte
+//   boundary).  Launch 3 reads 64 consecutive pixels of one (r, j) per wavefront: four whole lines.
+// Launch 3 (skyd_scale_kernel): one wavefront per (row, 64 pixels, chunk of SC scales), the lane owns a pixel.  x* = max_j x_j is known
+// from launch 2, so the x*-shifted sum of 3.18 needs one pass: per j one load of x and per live scale of the chunk one
+// exp(ln I0(a_i x) - ln I0(a_i x*)) <= 1.  ln I0(a_i x*) and the running sums of the SC scales sit in LDS ([scale][lane]: the lane
+// touches its own column only, so there is no barrier in the loop), the scale loop stays rolled and wf_log_i0 is instantiated twice.
+// It writes w_{p,i} to the w panel W[r][i][pix_pad], the pixel fastest again.
+// Launch 4 (skyd_finish_kernel): one workgroup per task over its n_z rows in order.  Per pixel (a thread, i ascending): mm_p = max_i
+// w, s_p = sum_i exp(w - mm_p), the moments; per scale (a wavefront, lanes over the pixels): m_i = max_p w, S_i = sum_p exp(w - m_i) in
+// the 2^-62 fixed point of sky_finish_kernel; over the pixels, in the same fixed point, total = sum_p exp(mm_p - M) s_p with M = max
+// w.  Every posterior is a difference first: post_sky = (mm_p - M) + (ln s_p - ln total), post_dist = (m_i - M) + (ln S_i - ln total),
+// post_joint = (w - M) - ln total, so the three sum to one to rounding where w ~ 1e6.  Integer sums over the pixels: their order does
+// not matter.  No atomics: a second call on the same inputs gives the same bits.
+//
+// Workspace (after alignment to 128 bytes), doubles: the sky call's layout (its u panel holds mm_p here), then [s_p: R x P][m_i: R x
+// n_a][S_i: R x n_a][X: R x n x pix_pad][W: R x n_a x pix_pad], the two panels on 128-byte boundaries.
+namespace npf {
+
+constexpr int kSkydSC = NPF_SKYD_SC;  // scales per wavefront of launch 3
+constexpr int kSkydFinishThreads = 256;
+constexpr int kSkydMaxScales = NPF_DIST_MAX_SCALES;
+
+struct SkydLayout {
+  SkyLayout sky;
+  int64_t ss, dm, ds, x, w, total;  // offsets in doubles; total < 0: the count does not fit int64
+};
+
+inline SkydLayout skyd_layout(int n_rows, int n_det, int pts, int n_pix, int n_tau, int n_a) {
+  SkydLayout L;
+  L.sky = sky_layout(n_rows, n_det, pts, n_pix, n_tau);
+  const int64_t n = n_tau > 0 ? n_tau : 1, rp = (int64_t)n_rows * n_pix, ra = (int64_t)n_rows * n_a;
+  L.ss = L.sky.total;
+  L.dm = L.ss + rp;
+  L.ds = L.dm + ra;
+  L.x = (L.ds + ra + 15) / 16 * 16;
+  // the panels: up to 2^24 rows x 2^16 grid times x 2^16 pixels
+  const unsigned __int128 rows_pp = (unsigned __int128)n_rows * (unsigned __int128)L.sky.pix_pad;
+  const unsigned __int128 xs = rows_pp * (unsigned __int128)n, wsz = rows_pp * (unsigned __int128)n_a;
+  const unsigned __int128 total = (unsigned __int128)L.x + xs + wsz;
+  if (total > (unsigned __int128)(INT64_MAX / 16)) {
+    L.w = L.total = -1;
+    return L;
+  }
+  L.w = L.x + (int64_t)xs;
+  L.total = (int64_t)total;
+  return L;
+}
+
+__device__ __forceinline__ bool skyd_scale_live(double a, double lp) {
+  return a > 0.0 && a < INFINITY && lp > -INFINITY && lp < INFINITY;  // (a NaN fails every test)
+}
+
+template <int JC>
+__global__ __launch_bounds__(64 * kSkyCorrWaves) void skyd_corr_kernel(
+    const double* __restrict__ hhk, const double2* __restrict__ step, const double2* __restrict__ start, const double2* __restrict__ U,
+    const double2* __restrict__ V, const double* __restrict__ resp, const double* __restrict__ log_prior, int n_rows, int n_det,
+    int n_pix, int pix_pad, int tp, int n_tau, int chunks, double* __restrict__ x_out, double* __restrict__ xm_out,
+    double* __restrict__ hh_out, int32_t* __restrict__ j_out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rt = blockIdx.x, pt = blockIdx.y * kSkyCorrWaves + wave;
+  if (pt * 16 >= n_pix) return;  // (no barrier below: a wavefront without a tile leaves)
+  const int tq = tp >> 2, kq = lane >> 4;
+  const size_t ks_max = (size_t)n_det * (size_t)tq;
+  const double2* up = U + (size_t)rt * ks_max * 64 + lane;
+  const double2* vp = V + (size_t)pt * ks_max * 64 + lane;
+  const int n = n_tau > 0 ? n_tau : 1;
+  const int p = pt * 16 + (lane & 15);  // (< pix_pad: the tile lies inside the padded panel)
+
+  // per (row, pixel) of the lane's four C/D registers: the running maximum of x_j and its first j
+  double best[4];
+  int best_j[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) best[q] = 0.0, best_j[q] = 0;
+
+  for (int chunk = 0; chunk < chunks; ++chunk) {
+    const int j0 = chunk * JC, nj = n_tau > 0 ? (n_tau - j0 < JC ? n_tau - j0 : JC) : 1;
+    sky_f64x4 acc_re[JC], acc_im[JC];
+#pragma unroll
+    for (int i = 0; i < JC; ++i) acc_re[i] = sky_f64x4{0.0, 0.0, 0.0, 0.0}, acc_im[i] = sky_f64x4{0.0, 0.0, 0.0, 0.0};
+    const double2* st = start + (size_t)chunk * (size_t)tp;
+    if (nj == JC) {
+      sky_chunk<JC, true>(up, vp, step, st, n_det, tq, kq, nj, acc_re, acc_im);
+    } else {
+      sky_chunk<JC, false>(up, vp, step, st, n_det, tq, kq, nj, acc_re, acc_im);
+    }
+#pragma unroll
+    for (int i = 0; i < JC; ++i) {
+      if (i < nj) {
+        const int j = j0 + i;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = rt * 16 + (lane >> 4) + 4 * q;  // the f64 C/D fragment: row = (lane >> 4) + 4 * reg
+          const double re = acc_re[i][q], im = acc_im[i][q], x = sqrt(re * re + im * im);
+          if (j == 0) {  // (j = 0 always enters, so a NaN there stays)
+            best[q] = x, best_j[q] = 0;
+          } else if (x > best[q]) {  // (j ascends: the smallest index stays)
+            best[q] = x;
+            best_j[q] = j;
+          }
+          if (r < n_rows) x_out[((size_t)r * (size_t)n + (size_t)j) * (size_t)pix_pad + (size_t)p] = x;  // 16 lanes: one 128-byte line
+        }
+      }
+    }
+  }
+
+  if (p >= n_pix) return;
+  const bool live = sky_pixel_live(log_prior, p);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = rt * 16 + (lane >> 4) + 4 * q;
+    if (r >= n_rows) continue;
+    const size_t o = (size_t)r * (size_t)n_pix + (size_t)p;
+    if (!live) {  // no mass; nothing of its resp is read
+      xm_out[o] = 0.0, hh_out[o] = 0.0, j_out[o] = 0;
+      continue;
+    }
+    double hh = 0.0;
+    for (int k = 0; k < n_det; ++k) {  // HH_p = sum_k |C_{p,k}|^2 hh_k, k ascending
+      const double c_re = resp[2 * ((size_t)p * n_det + k)], c_im = resp[2 * ((size_t)p * n_det + k) + 1];
+      hh += (c_re * c_re + c_im * c_im) * hhk[(size_t)r * (size_t)n_det + (size_t)k];
+    }
+    xm_out[o] = best[q];
+    hh_out[o] = hh;
+    j_out[o] = best_j[q];
+  }
+}
+
+template <int SC>
+__global__ __launch_bounds__(64) void skyd_scale_kernel(const double* __restrict__ x_ws, const double* __restrict__ xm_ws,
+                                                         const double* __restrict__ hh_ws, const double* __restrict__ log_prior,
+                                                         const double* __restrict__ scales, const double* __restrict__ log_prior_scale,
+                                                         int n_pix, int pix_pad, int n_tau, int n_a, double* __restrict__ w_ws) {
+  __shared__ double sc_a[SC], sc_lp[SC];             // a_i (0: dead or beyond n_a), ln pi_i
+  __shared__ double l0_s[SC][64], sum_s[SC][64];     // ln I0(a_i x*), the shifted sum over j: [scale][lane]
+  const int lane = threadIdx.x, r = blockIdx.x, p = blockIdx.y * 64 + lane, i0 = blockIdx.z * SC;
+  const int n = n_tau > 0 ? n_tau : 1;
+  if (lane < SC) {
+    const int i = i0 + lane;
+    double a = 0.0, lp = 0.0;
+    if (i < n_a) a = scales[i], lp = log_prior_scale[i];
+    const bool ok = i < n_a && skyd_scale_live(a, lp);
+    sc_a[lane] = ok ? a : 0.0;
+    sc_lp[lane] = ok ? lp : 0.0;
+  }
+  __syncthreads();
+  const bool in = p < n_pix;
+  const bool live = in && sky_pixel_live(log_prior, p);
+  const size_t o = (size_t)r * (size_t)n_pix + (size_t)(in ? p : 0);
+  const double hh = live ? hh_ws[o] : 0.0;
+  const bool degenerate = hh == 0.0;  // Lambda = 1 at every scale: x_j = 0 (a dead or padding lane as well; its w is -inf below)
+  const double xb = degenerate ? 0.0 : xm_ws[o];
+#pragma unroll 1
+  for (int k = 0; k < SC; ++k) {
+    const double a = sc_a[k];
+    if (a == 0.0) continue;  // (the same for every lane)
+    l0_s[k][lane] = wf_log_i0(a * xb);
+    sum_s[k][lane] = 0.0;
+  }
+  const double* xc = x_ws + (size_t)r * (size_t)n * (size_t)pix_pad + (size_t)(in ? p : 0);
+#pragma unroll 1
+  for (int j = 0; j < n; ++j) {
+    const double x = degenerate ? 0.0 : xc[(size_t)j * (size_t)pix_pad];
+#pragma unroll 1
+    for (int k = 0; k < SC; ++k) {
+      const double a = sc_a[k];
+      if (a == 0.0) continue;
+      sum_s[k][lane] += exp(wf_log_i0(a * x) - l0_s[k][lane]);
+    }
+  }
+  if (!in) return;
+  const double lp = log_prior ? log_prior[p] : -log((double)n_pix);
+  const double log_n = log((double)n);
+#pragma unroll 1
+  for (int k = 0; k < SC; ++k) {
+    const int i = i0 + k;
+    if (i >= n_a) break;
+    const double a = sc_a[k];
+    double w = -INFINITY;
+    if (live && a != 0.0) w = lp + ((sc_lp[k] + (l0_s[k][lane] - (a * a) * (0.5 * hh))) + (log(sum_s[k][lane]) - log_n));
+    w_ws[((size_t)r * (size_t)n_a + (size_t)i) * (size_t)pix_pad + (size_t)p] = w;
+  }
+}
+
+// max with the smallest index over the workgroup (a NaN never enters); every thread gets the same bits
+template <int THREADS>
+__device__ __forceinline__ void skyd_block_argmax(double& best, int& idx, double* red_v, int* red_i) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double ob = __shfl_xor(best, off);
+    const int oi = __shfl_xor(idx, off);
+    if (ob > best || (ob == best && oi < idx)) best = ob, idx = oi;
+  }
+  __syncthreads();  // (red_* may still be read for the previous reduction)
+  if (lane == 0) red_v[wave] = best, red_i[wave] = idx;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < THREADS / 64; ++w) {
+    const double ob = red_v[w];
+    const int oi = red_i[w];
+    if (w == 0 || ob > best || (ob == best && oi < idx)) best = ob, idx = oi;
+  }
+}
+
+// e in [0, 2^31) enters the 2^-62 fixed-point sum (hi: units of 2^-30, lo: units of 2^-62)
+__device__ __forceinline__ void skyd_fixed_add(long long& hi, long long& lo, double e) {
+  const double scaled = e * 0x1p30, fl = floor(scaled);
+  hi += (long long)fl;
+  lo += (long long)floor((scaled - fl) * 0x1p32);
+}
+
+// One workgroup per task: its n_z = n_rows / n_tasks rows in order, then the mixtures over them.
+__global__ __launch_bounds__(kSkydFinishThreads) void skyd_finish_kernel(
+    const double* __restrict__ w_ws, const double* __restrict__ xm_ws, const double* __restrict__ hh_ws, const int32_t* __restrict__ j_ws,
+    const double* __restrict__ scales, double* mm_ws, double* ss_ws, double* dm_ws, double* ds_ws, int n_rows, int n_tasks, int n_pix,
+    int pix_pad, int n_a, double* __restrict__ lnl_vol, int32_t* __restrict__ pix_index, int32_t* __restrict__ scale_index,
+    int32_t* __restrict__ tau_index, double* __restrict__ snr, double* __restrict__ scale_hat, double* __restrict__ lnl,
+    double* __restrict__ post_sky, double* __restrict__ post_dist, double* __restrict__ post_joint, double* __restrict__ dist_mean,
+    double* __restrict__ dist_std, double* __restrict__ post_sky_mix, double* __restrict__ post_dist_mix) {
+  constexpr int THREADS = kSkydFinishThreads, WAVES = THREADS / 64;
+  __shared__ double red_v[WAVES];
+  __shared__ int red_i[WAVES];
+  __shared__ long long red_hi[WAVES], red_lo[WAVES];
+  __shared__ int red_nan[WAVES];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n_z = n_rows / n_tasks;
+  const size_t pp = (size_t)pix_pad;
+  double mix_m = 0.0, mix_s = 0.0;  // (every thread carries the same running log-sum-exp over the rows)
+
+  for (int s = 0; s < n_z; ++s) {
+    const int r = s * n_tasks + b;
+    const double* W = w_ws + (size_t)r * (size_t)n_a * pp;
+    double* mm = mm_ws + (size_t)r * (size_t)n_pix;
+    double* ss = ss_ws + (size_t)r * (size_t)n_pix;
+    double* dm = dm_ws + (size_t)r * (size_t)n_a;
+    double* ds = ds_ws + (size_t)r * (size_t)n_a;
+
+    // per pixel, i ascending: mm_p, s_p, u_sky = mm_p + ln s_p and the moments of 1 / a about the pixel's own weights
+    double best_u = -INFINITY, w_max = -INFINITY;
+    int best_p = n_pix, dummy = 0;
+    for (int p = tid; p < n_pix; p += THREADS) {
+      double m = -INFINITY;
+      for (int i = 0; i < n_a; ++i) {
+        const double v = W[(size_t)i * pp + p];
+        if (v > m) m = v;  // (a NaN never enters)
+      }
+      double sum = 0.0, acc = 0.0;
+      for (int i = 0; i < n_a; ++i) {
+        const double v = W[(size_t)i * pp + p];
+        if (v == -INFINITY) continue;  // a dead scale or a dead pixel: no mass, and its a_i is not used
+        const double e = exp(v - m);
+        sum += e;
+        acc += (1.0 / scales[i]) * e;
+      }
+      mm[p] = m;
+      ss[p] = sum;
+      const double u = sum == 0.0 ? -INFINITY : m + log(sum);
+      if (u > best_u) best_u = u, best_p = p;  // (p ascends: the smallest index of the thread stays)
+      if (m > w_max) w_max = m;
+      if (dist_mean || dist_std) {
+        const size_t o = (size_t)r * (size_t)n_pix + (size_t)p;
+        const double mean = sum == 0.0 ? 0.0 : acc / sum;
+        if (dist_mean) dist_mean[o] = mean;
+        if (dist_std) {
+          double var = 0.0;  // the second pass about the mean
+          for (int i = 0; i < n_a; ++i) {
+            const double v = W[(size_t)i * pp + p];
+            if (v == -INFINITY) continue;
+            const double dv = 1.0 / scales[i] - mean;
+            var += (dv * dv) * exp(v - m);
+          }
+          dist_std[o] = sum == 0.0 ? 0.0 : sqrt(var / sum);
+        }
+      }
+    }
+    skyd_block_argmax<THREADS>(best_u, best_p, red_v, red_i);
+    skyd_block_argmax<THREADS>(w_max, dummy, red_v, red_i);
+
+    // total = sum_p exp(mm_p - M) s_p in 2^-62 fixed point: integer sums do not depend on the order of the pixels
+    long long hi = 0, lo = 0;
+    int any_nan = 0;
+    for (int p = tid; p < n_pix; p += THREADS) {
+      const double sum = ss[p];
+      if (sum == 0.0) continue;                   // no mass
+      const double e = exp(mm[p] - w_max) * sum;  // in [0, n_a]; NaN where w is NaN at the pixel
+      if (!(e >= 0.0)) {
+        any_nan = 1;
+        continue;
+      }
+      skyd_fixed_add(hi, lo, e);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      hi += __shfl_xor(hi, off);
+      lo += __shfl_xor(lo, off);
+      any_nan |= __shfl_xor(any_nan, off);
+    }
+    __syncthreads();
+    if (lane == 0) red_hi[wave] = hi, red_lo[wave] = lo, red_nan[wave] = any_nan;
+    __syncthreads();
+    hi = 0, lo = 0, any_nan = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) hi += red_hi[w], lo += red_lo[w], any_nan |= red_nan[w];
+    const bool none = best_p == n_pix;  // no pixel with mass (every thread: the same bits)
+    const double log_total = any_nan ? NAN : log((double)hi * 0x1p-30 + (double)lo * 0x1p-62);
+    const double v_vol = any_nan ? NAN : (none ? -INFINITY : w_max + log_total);
+    const int p_star = none ? 0 : best_p;
+
+    // per scale, a wavefront each, the lanes over the pixels: m_i and S_i in the same fixed point
+    for (int i = wave; i < n_a; i += WAVES) {
+      const double* Wi = W + (size_t)i * pp;
+      double m = -INFINITY;
+      for (int p = lane; p < n_pix; p += 64) {
+        const double v = Wi[p];
+        if (v > m) m = v;
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const double om = __shfl_xor(m, off);
+        if (om > m) m = om;
+      }
+      long long h2 = 0, l2 = 0;
+      int nan2 = 0;
+      for (int p = lane; p < n_pix; p += 64) {
+        const double v = Wi[p];
+        if (v == -INFINITY) continue;
+        const double e = exp(v - m);  // in [0, 1]
+        if (!(e >= 0.0)) {
+          nan2 = 1;
+          continue;
+        }
+        skyd_fixed_add(h2, l2, e);
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        h2 += __shfl_xor(h2, off);
+        l2 += __shfl_xor(l2, off);
+        nan2 |= __shfl_xor(nan2, off);
+      }
+      if (lane == 0) {
+        dm[i] = m;
+        ds[i] = nan2 ? NAN : (double)h2 * 0x1p-30 + (double)l2 * 0x1p-62;
+      }
+    }
+    __syncthreads();  // (dm, ds of every scale are written)
+
+    double best_d = -INFINITY;
+    int best_i = n_a;
+    for (int i = tid; i < n_a; i += THREADS) {
+      const double sum = ds[i], u = sum == 0.0 ? -INFINITY : dm[i] + log(sum);
+      if (u > best_d) best_d = u, best_i = i;
+    }
+    skyd_block_argmax<THREADS>(best_d, best_i, red_v, red_i);
+
+    if (tid == 0) {
+      const size_t o = (size_t)r * (size_t)n_pix + (size_t)p_star;
+      const double hh = none ? 0.0 : hh_ws[o];  // (a dead pixel holds 0 here)
+      if (lnl_vol) lnl_vol[r] = v_vol;
+      if (pix_index) pix_index[r] = p_star;
+      if (scale_index) scale_index[r] = best_i == n_a ? 0 : best_i;
+      if (tau_index) tau_index[r] = none ? 0 : j_ws[o];
+      if (snr) snr[r] = hh == 0.0 ? 0.0 : xm_ws[o] / sqrt(hh);
+      if (scale_hat) scale_hat[r] = hh == 0.0 ? 0.0 : xm_ws[o] / hh;
+    }
+    if (post_sky) {
+      for (int p = tid; p < n_pix; p += THREADS) {
+        const double sum = ss[p];
+        post_sky[(size_t)r * (size_t)n_pix + (size_t)p] = sum == 0.0 ? -INFINITY : (mm[p] - w_max) + (log(sum) - log_total);
+      }
+    }
+    if (post_dist) {
+      for (int i = tid; i < n_a; i += THREADS) {
+        const double sum = ds[i];
+        post_dist[(size_t)r * (size_t)n_a + (size_t)i] = sum == 0.0 ? -INFINITY : (dm[i] - w_max) + (log(sum) - log_total);
+      }
+    }
+    if (post_joint) {
+      double* dst = post_joint + (size_t)r * (size_t)n_pix * (size_t)n_a;
+      const size_t cells = (size_t)n_pix * (size_t)n_a;
+      for (size_t c = tid; c < cells; c += THREADS) {  // [p][i], the scale fastest
+        const size_t p = c / (size_t)n_a, i = c - p * (size_t)n_a;
+        const double v = W[i * pp + p];
+        dst[c] = v == -INFINITY ? -INFINITY : (v - w_max) - log_total;
+      }
+    }
+    sky_lse_add(mix_m, mix_s, v_vol);
+  }
+
+  const double log_nz = log((double)n_z);
+  const double v_mix = mix_s == 0.0 ? -INFINITY : mix_m + (log(mix_s) - log_nz);
+  if (tid == 0 && lnl) lnl[b] = v_mix;
+  if (post_sky_mix) {
+    for (int p = tid; p < n_pix; p += THREADS) {
+      double m = 0.0, sm = 0.0;
+      for (int s = 0; s < n_z; ++s) {
+        const size_t o = (size_t)(s * n_tasks + b) * (size_t)n_pix + (size_t)p;
+        const double sum = ss_ws[o];
+        sky_lse_add(m, sm, sum == 0.0 ? -INFINITY : mm_ws[o] + log(sum));
+      }
+      post_sky_mix[(size_t)b * (size_t)n_pix + (size_t)p] = sm == 0.0 ? -INFINITY : (m + (log(sm) - log_nz)) - v_mix;
+    }
+  }
+  if (post_dist_mix) {
+    for (int i = tid; i < n_a; i += THREADS) {
+      double m = 0.0, sm = 0.0;
+      for (int s = 0; s < n_z; ++s) {
+        const size_t o = (size_t)(s * n_tasks + b) * (size_t)n_a + (size_t)i;
+        const double sum = ds_ws[o];
+        sky_lse_add(m, sm, sum == 0.0 ? -INFINITY : dm_ws[o] + log(sum));
+      }
+      post_dist_mix[(size_t)b * (size_t)n_a + (size_t)i] = sm == 0.0 ? -INFINITY : (m + (log(sm) - log_nz)) - v_mix;
+    }
+  }
+}
+
+}  // namespace npf
+
+extern "C" int64_t npf_waveform_loglike_sky_dist_workspace_bytes(int32_t n_rows, int32_t n_det, int32_t pts, int32_t n_pix, int32_t n_tau,
+                                                                 int32_t n_a) {
+  using namespace npf;
+  if (sky_sizes_bad(n_rows, n_det, pts, n_pix, n_tau) || n_a < 1 || n_a > kSkydMaxScales) return NPF_EINVAL;
+  const SkydLayout L = skyd_layout(n_rows, n_det, pts, n_pix, n_tau, n_a);
+  if (L.total < 0) return NPF_EINVAL;  // the panels' count does not fit int64
+  return L.total * (int64_t)sizeof(double) + 128;  // (+ 128: the panels are aligned to 128 bytes)
+}
+
+extern "C" int npf_waveform_loglike_sky_dist(const float* h, int32_t h_ld, const float* d, const float* wgt, int32_t wgt_rows,
+                                             const float* freq, int32_t freq_rows, const int32_t* n_valid, const double* resp,
+                                             const double* delay, const double* log_prior, int32_t n_rows, int32_t n_tasks,
+                                             int32_t n_det, int32_t pts, int32_t n_pix, double tau0, double dtau, int32_t n_tau,
+                                             const double* scales, const double* log_prior_scale, int32_t n_a, double* lnl_vol,
+                                             int32_t* pix_index, int32_t* scale_index, int32_t* tau_index, double* snr, double* scale_hat,
+                                             double* lnl, double* post_sky, double* post_dist, double* post_joint, double* dist_mean,
+                                             double* dist_std, double* post_sky_mix, double* post_dist_mix, void* workspace, void* stream) {
+  using namespace npf;
+  if (wf_loglike_net_args_bad(h, h_ld, d, wgt, wgt_rows, freq, freq_rows, delay, resp, n_rows, n_tasks, n_det, pts, n_tau, workspace))
+    return NPF_EINVAL;
+  if (!freq || freq_rows != 1 || sky_sizes_bad(n_rows, n_det, pts, n_pix, n_tau)) return NPF_EINVAL;
+  if (!scales || !log_prior_scale || n_a < 1 || n_a > kSkydMaxScales) return NPF_EINVAL;
+  if (!lnl_vol && !pix_index && !scale_index && !tau_index && !snr && !scale_hat && !lnl && !post_sky && !post_dist && !post_joint &&
+      !dist_mean && !dist_std && !post_sky_mix && !post_dist_mix)
+    return NPF_EINVAL;
+  const SkydLayout D = skyd_layout(n_rows, n_det, pts, n_pix, n_tau, n_a);
+  if (D.total < 0) return NPF_EINVAL;
+  if (n_tau == 0) tau0 = dtau = 0.0;  // the one candidate is tau = 0
+  const SkyLayout& L = D.sky;
+  double* ws = reinterpret_cast<double*>(((uintptr_t)workspace + 127) & ~(uintptr_t)127);
+  double2 *step = (double2*)(ws + L.step), *start = (double2*)(ws + L.start), *U = (double2*)(ws + L.u), *V = (double2*)(ws + L.v);
+  int32_t* jx = reinterpret_cast<int32_t*>(ws + L.jx);
+  hipStream_t st = (hipStream_t)stream;
+
+  const int64_t prep_blocks = L.rows_pad + L.pix_pad + 1 + L.chunks;
+  hipLaunchKernelGGL((sky_prep_kernel<kSkyJC, kSkyPrepThreads>), dim3((unsigned)prep_blocks), dim3(kSkyPrepThreads), 0, st, h, h_ld, d, wgt,
+                     (int)(wgt_rows != 1), freq, n_valid, resp, delay, log_prior, n_rows, n_tasks, n_det, pts, n_pix, tau0, dtau, n_tau,
+                     (int)L.rows_pad, (int)L.pix_pad, (int)L.tp, ws + L.hhk, step, start, U, V);
+  NPF_CHECK_LAUNCH();
+  const int64_t pix_tiles = L.pix_pad / 16;
+  hipLaunchKernelGGL(skyd_corr_kernel<kSkyJC>, dim3((unsigned)(L.rows_pad / 16), (unsigned)((pix_tiles + kSkyCorrWaves - 1) / kSkyCorrWaves)),
+                     dim3(64 * kSkyCorrWaves), 0, st, ws + L.hhk, step, start, U, V, resp, log_prior, n_rows, n_det, n_pix, (int)L.pix_pad,
+                     (int)L.tp, n_tau, (int)L.chunks, ws + D.x, ws + L.xm, ws + L.hh, jx);
+  NPF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(skyd_scale_kernel<kSkydSC>, dim3((unsigned)n_rows, (unsigned)((n_pix + 63) / 64), (unsigned)((n_a + kSkydSC - 1) / kSkydSC)),
+                     dim3(64), 0, st, ws + D.x, ws + L.xm, ws + L.hh, log_prior, scales, log_prior_scale, n_pix, (int)L.pix_pad, n_tau, n_a,
+                     ws + D.w);
+  NPF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(skyd_finish_kernel, dim3(n_tasks), dim3(kSkydFinishThreads), 0, st, ws + D.w, ws + L.xm, ws + L.hh, jx, scales, ws + L.lu,
+                     ws + D.ss, ws + D.dm, ws + D.ds, n_rows, n_tasks, n_pix, (int)L.pix_pad, n_a, lnl_vol, pix_index, scale_index, tau_index,
+                     snr, scale_hat, lnl, post_sky, post_dist, post_joint, dist_mean, dist_std, post_sky_mix, post_dist_mix);
+  NPF_CHECK_LAUNCH();
+  return NPF_OK;
+}

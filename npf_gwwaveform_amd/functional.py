@@ -848,7 +848,7 @@ def waveform_loglike_sky(h: torch.Tensor, data: torch.Tensor, response: torch.Te
     matrix instruction -- the rotation by ``tau_j`` is done once per row, not once per pixel -- in three launches; inference only,
     no host sync, deterministic; the workspace is the one of :func:`waveform_match`.
     Out of scope: antenna patterns and delays from (ra, dec, psi, iota), which come from the caller's GW library; a sky grid per
-    task; gradients; distance marginalised jointly with the sky; adaptive or hierarchical pixel refinement."""
+    task; gradients; adaptive or hierarchical pixel refinement (distance jointly with the sky: :func:`waveform_loglike_sky_distance`)."""
     if isinstance(want, str) or not isinstance(want, (tuple, list)) or any(w not in LOGLIKE_SKY_NAMES for w in want):
         raise ValueError(f"want must be a tuple / list of names out of {LOGLIKE_SKY_NAMES}, got {want!r}")
     want = tuple(want)
@@ -1210,6 +1210,116 @@ def distance_prior(distances: torch.Tensor, d_ref: float, power: float = 2.0):
         width = 0.5 * (torch.nn.functional.pad(gap, (1, 0)) + torch.nn.functional.pad(gap, (0, 1)))
     lp = float(power) * torch.log(d) + torch.log(width)
     return float(d_ref) / d, lp - torch.logsumexp(lp, -1, keepdim=True)
+
+
+# ---- sky and distance marginalised jointly (csrc/waveform_sky_kernels.hip) --------------
+SKYD_SC = 8  # NPF_SKYD_SC: scales per wavefront of the scale-marginal launch
+LOGLIKE_SKY_DIST_NAMES = ("lnl_vol", "pix_index", "scale_index", "tau_index", "snr", "scale_hat", "lnl")
+
+
+class WaveformLogLikeSkyDistance(NamedTuple):
+    """What :func:`waveform_loglike_sky_distance` returns (float64 but the three indices); what was not asked for is ``None``."""
+    lnl_vol: Optional[torch.Tensor]        # [R] phase, time, sky position and distance marginalised
+    pix_index: Optional[torch.Tensor]      # [R] int32: the pixel of the largest distance-marginal evidence, the smallest index
+    scale_index: Optional[torch.Tensor]    # [R] int32: the scale of the largest sky-marginal evidence, the smallest index
+    tau_index: Optional[torch.Tensor]      # [R] int32: the grid time of the largest |K_j| at pixel pix_index
+    snr: Optional[torch.Tensor]            # [R] max_j |K_j| / sqrt(HH) at that pixel
+    scale_hat: Optional[torch.Tensor]      # [R] max_j |K_j| / HH at that pixel: the maximum-likelihood scale there
+    lnl: Optional[torch.Tensor]            # [B] lnl_vol marginalised over the latent samples
+    post_sky: Optional[torch.Tensor]       # [R, P] the sky map, distance marginalised (``posterior=True``)
+    post_dist: Optional[torch.Tensor]      # [R, n_a] the distance posterior, sky marginalised (``posterior=True``)
+    post_sky_mix: Optional[torch.Tensor]   # [B, P] (``posterior=True``)
+    post_dist_mix: Optional[torch.Tensor]  # [B, n_a] (``posterior=True``)
+    post_joint: Optional[torch.Tensor]     # [R, P, n_a] (``joint=True``)
+    dist_mean: Optional[torch.Tensor]      # [R, P] E[d / d_ref | pixel] (``moments=True``)
+    dist_std: Optional[torch.Tensor]       # [R, P] its spread (``moments=True``)
+
+
+def check_loglike_sky_distance_args(h_shape, data, response, delays, scales, log_prior_scale, log_prior=None, weights=None, freqs=None,
+                                    taus=None):
+    """The shapes and dtypes of a :func:`waveform_loglike_sky_distance` call -> ``(geo, n_a)`` with ``geo`` what
+    :func:`check_loglike_sky_args` returns, under its rules; ``scales`` and ``log_prior_scale``: float64 tensors [n_a], ``1 <= n_a <=
+    DIST_MAX_SCALES`` -- one grid shared by the tasks, so [B, n_a] is refused.  ``ValueError`` for anything that does not fit.
+    Reads no data."""
+    geo = check_loglike_sky_args(h_shape, data, response, delays, log_prior, weights, freqs, taus)
+    n_a = None
+    for t, what in ((scales, "scales"), (log_prior_scale, "log_prior_scale")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.float64:
+            raise ValueError(f"{what} must be a float64 tensor of shape [n_a] (one scale grid shared by the tasks), got "
+                             f"{(list(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if not 1 <= t.shape[0] <= DIST_MAX_SCALES:
+            raise ValueError(f"{what} holds {t.shape[0]} scales: 1 <= n_a <= {DIST_MAX_SCALES}")
+        if n_a is not None and t.shape[0] != n_a:
+            raise ValueError(f"scales holds {n_a} grid points, log_prior_scale {t.shape[0]}")
+        n_a = t.shape[0]
+    return geo, n_a
+
+
+def waveform_loglike_sky_distance(h: torch.Tensor, data: torch.Tensor, response: torch.Tensor, delays: torch.Tensor,
+                                  scales: torch.Tensor, log_prior_scale: torch.Tensor, log_prior: Optional[torch.Tensor] = None,
+                                  weights: Optional[torch.Tensor] = None, freqs: Optional[torch.Tensor] = None, taus=None,
+                                  n_valid: Optional[torch.Tensor] = None, want=LOGLIKE_SKY_DIST_NAMES, posterior: bool = False,
+                                  joint: bool = False, moments: bool = False) -> WaveformLogLikeSkyDistance:
+    """The likelihood of :func:`waveform_loglike_sky` marginalised over the amplitude scale of the template as well: sky and
+    distance jointly, in one call.  ``h``, ``data``, ``response`` [P, D, 2], ``delays`` [P, D], ``log_prior`` [P] (pixels),
+    ``weights``, ``freqs`` [T], ``taus``, ``n_valid``: as in :func:`waveform_loglike_sky`; ``scales`` [n_a] (``a_i``) and
+    ``log_prior_scale`` [n_a] (``ln pi_i``; :func:`distance_prior` makes both) are float64 DEVICE tensors shared by the tasks, under
+    the liveness rule of :func:`waveform_loglike_distance`; the host reads neither.  With ``x_{p,j} = |K_{j,p}|``:
+    ``w_{p,i} = log_prior_p + ln pi_i + (logsumexp_j ln I0(a_i x_{p,j}) - ln n) - a_i^2 HH_p / 2`` (``-inf`` for a dead pixel or
+    scale), ``lnl_vol = logsumexp_{p,i} w``, ``pix_index`` / ``scale_index`` the smallest index of the largest marginal evidence
+    over the other axis, ``tau_index`` / ``snr`` as in the sky call at ``pix_index``, ``scale_hat = x* / HH`` there, ``lnl`` [B] the
+    log-mean-exp of ``lnl_vol`` over the latent samples.  ``posterior=True`` adds ``post_sky`` [R, P], ``post_dist`` [R, n_a] and
+    their mixtures [B, .]; ``joint=True`` ``post_joint`` [R, P, n_a]; ``moments=True`` ``dist_mean`` / ``dist_std`` [R, P], the
+    conditional mean and spread of ``1 / a = d / d_ref`` at every pixel (0 at a dead pixel).  ``want``: names out of
+    ``LOGLIKE_SKY_DIST_NAMES``.  ``npf_waveform_loglike_sky_dist``: four launches, double arithmetic, inference only, no host
+    sync, deterministic; the workspace is the one of :func:`waveform_match`.  ``include/npf_hip.h`` has the contract.
+    Out of scope: gradients; per-task or per-pixel scale grids; moments of the mixture over the latent samples; antenna patterns
+    from angles; adaptive pixel refinement; continuous amplitude integration."""
+    names = LOGLIKE_SKY_DIST_NAMES
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or any(w not in names for w in want):
+        raise ValueError(f"want must be a tuple / list of names out of {names}, got {want!r}")
+    want = tuple(want)
+    geo, n_a = check_loglike_sky_distance_args(getattr(h, "shape", ()), data, response, delays, scales, log_prior_scale, log_prior,
+                                               weights, freqs, taus)
+    R, T, ld, B, D, P, wgt_rows, tau0, dtau, n_tau = geo
+    if not want and not posterior and not joint and not moments:
+        raise ValueError(f"want must name at least one of {names} (or posterior=True / joint=True / moments=True)")
+    for t, what in ((h, "h"), (data, "data"), (response, "response"), (delays, "delays"), (scales, "scales"),
+                    (log_prior_scale, "log_prior_scale"), (log_prior, "log_prior"), (weights, "weights"), (freqs, "freqs")):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"waveform_loglike_sky_distance is inference only: {what} requires grad; detach it")
+    for t in (h, data, weights, freqs):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError("the HIP path takes fp32 device tensors only; there is no CPU fallback")
+    for t, what in ((response, "response"), (delays, "delays"), (log_prior, "log_prior"), (scales, "scales"),
+                    (log_prior_scale, "log_prior_scale")):
+        if t is not None and (not t.is_cuda or t.device != h.device):
+            raise ValueError(f"{what} must live on the device of h ({h.device}), got {t.device}: the kernel reads it there")
+    h, data, freqs = h.contiguous(), data.contiguous(), freqs.contiguous()
+    response, delays = response.contiguous(), delays.contiguous()
+    scales, log_prior_scale = scales.contiguous(), log_prior_scale.contiguous()
+    log_prior = log_prior.contiguous() if log_prior is not None else None
+    weights = weights.contiguous() if weights is not None else None
+    nv = counts_i32(n_valid, B) if n_valid is not None else None
+    lib = L.load()
+    nbytes = int(lib.npf_waveform_loglike_sky_dist_workspace_bytes(R, D, T, P, n_tau, n_a))
+    if nbytes < 0:
+        raise ValueError(f"the workspace of {R} rows x {P} pixels x max({n_tau}, {n_a}) grid points does not fit a 64-bit byte count")
+    ws = _match_workspace(h.device, nbytes)
+    out = {name: (torch.empty((B if name == "lnl" else R,), dtype=torch.int32 if name.endswith("index") else torch.float64,
+                              device=h.device) if name in want else None) for name in names}
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=h.device)  # noqa: E731
+    post_sky, post_dist, sky_mix, dist_mix = (new(R, P), new(R, n_a), new(B, P), new(B, n_a)) if posterior else (None,) * 4
+    post_joint = new(R, P, n_a) if joint else None
+    mean, std = (new(R, P), new(R, P)) if moments else (None, None)
+    dptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    L.check(lib.npf_waveform_loglike_sky_dist(L.ptr(h), ld, L.ptr(data), L.ptr(weights), wgt_rows, L.ptr(freqs), 1,
+                                              _iptr(nv) if nv is not None else None, dptr(response), dptr(delays), dptr(log_prior), R,
+                                              B, D, T, P, tau0, dtau, n_tau, dptr(scales), dptr(log_prior_scale), n_a,
+                                              *(dptr(out[name]) for name in names), dptr(post_sky), dptr(post_dist), dptr(post_joint),
+                                              dptr(mean), dptr(std), dptr(sky_mix), dptr(dist_mix), ws.data_ptr(), L.stream_ptr()),
+            "npf_waveform_loglike_sky_dist")
+    return WaveformLogLikeSkyDistance(*(out[name] for name in names), post_sky, post_dist, sky_mix, dist_mix, post_joint, mean, std)
 
 
 # ---- Monte-Carlo objectives over the latent samples -------------------------------------

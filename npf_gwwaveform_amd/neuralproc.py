@@ -31,7 +31,7 @@ from .architectures import (MLP, DotAttender, KeyWeights, LeaveOneOut, MergeFlat
 from .chain import Chain, PTensor, pad32, pt_shape
 
 __all__ = ["NeuralProcessFamily", "LatentNeuralProcessFamily", "CNP", "LNP", "AttnCNP", "AttnLNP",
-           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "BankMatch", "LogLike", "NetworkLogLike", "SkyLogLike", "DistanceLogLike",
+           "MultivariateNormalDiag", "HeadDistribution", "Conditioned", "Prediction", "Score", "Match", "BankMatch", "LogLike", "NetworkLogLike", "SkyLogLike", "SkyDistanceLogLike", "DistanceLogLike",
            "NetworkDistanceLogLike", "Reweighted", "bootstrap_weights",
            "kfold_weights"]
 
@@ -134,6 +134,28 @@ class SkyLogLike(NamedTuple):
     post: Optional[torch.Tensor]       # [.., B, P] log posterior mass of every pixel: the sky map (``posterior=True``)
     post_mix: Optional[torch.Tensor]   # [B, P] the same with the latent samples marginalised (``posterior=True``)
     snr_map: Optional[torch.Tensor]    # [.., B, P] the best network SNR of every pixel (``snr_map=True``)
+
+
+class SkyDistanceLogLike(NamedTuple):
+    """Sky and distance marginalised jointly (:meth:`HeadDistribution.loglike_sky_distance`), float64 (but the indices).  Per (latent
+    sample, task): [n_z, B] for ``of="samples"``, [1, B] for ``of="mean"``; per task: [B]; per pixel / scale: a last axis of ``P`` /
+    ``n_a``."""
+    lnl: torch.Tensor                      # [B] lnl_vol marginalised over the latent samples: log-mean-exp
+    lnl_vol: torch.Tensor                  # ln Lambda marginalised over phase, grid times, sky pixels and amplitude scales
+    pix_index: torch.Tensor                # int32: the pixel of the largest distance-marginal evidence, the smallest index
+    scale_index: torch.Tensor              # int32: the scale of the largest sky-marginal evidence, the smallest index
+    scale_map: torch.Tensor                # ``scales`` gathered there
+    tau_index: Optional[torch.Tensor]      # int32: the grid time of the largest |K_j| at pixel pix_index (``taus`` given)
+    tau: Optional[torch.Tensor]            # that grid time (``taus`` given)
+    snr: torch.Tensor                      # the network SNR at that pixel and grid time
+    scale_hat: torch.Tensor                # the maximum-likelihood scale at that pixel; distance d_ref / scale_hat
+    post_sky: Optional[torch.Tensor]       # [.., B, P] the sky map with the distance marginalised (``posterior=True``)
+    post_dist: Optional[torch.Tensor]      # [.., B, n_a] the distance posterior with the sky marginalised (``posterior=True``)
+    post_sky_mix: Optional[torch.Tensor]   # [B, P] the sky map with the latent samples marginalised too (``posterior=True``)
+    post_dist_mix: Optional[torch.Tensor]  # [B, n_a] the same of the distance posterior (``posterior=True``)
+    post_joint: Optional[torch.Tensor]     # [.., B, P, n_a] the joint log posterior mass (``joint=True``)
+    dist_mean: Optional[torch.Tensor]      # [.., B, P] E[d / d_ref | pixel]: with dist_std the volume map (``moments=True``)
+    dist_std: Optional[torch.Tensor]       # [.., B, P] the spread of d / d_ref at the pixel (``moments=True``)
 
 
 class DistanceLogLike(NamedTuple):
@@ -472,7 +494,7 @@ class HeadDistribution(Independent):
         be captured in one graph (call once at the sizes before capturing) and replayed after ``response`` / ``delays`` /
         ``log_prior`` were overwritten in place.
         Out of scope: antenna patterns and delays from (ra, dec, psi, iota), which come from the caller's GW library; a sky grid
-        per task; gradients; distance marginalised jointly with the sky; adaptive or hierarchical pixel refinement."""
+        per task; gradients; adaptive or hierarchical pixel refinement (distance jointly with the sky: :meth:`loglike_sky_distance`)."""
         if self._y_dim != 2:
             raise ValueError(f"loglike_sky needs a model whose two outputs are (amplitude, phase): y_dim == 2, got {self._y_dim}")
         if of not in ("samples", "mean"):
@@ -490,6 +512,43 @@ class HeadDistribution(Independent):
                               m.tau_index.view(lead) if taus is not None else None, tau, m.snr.view(lead),
                               m.post.view(*lead, P) if posterior else None, m.post_mix,
                               m.snr_map.view(*lead, P) if snr_map else None)
+
+    def loglike_sky_distance(self, data, response, delays, scales, log_prior_scale, log_prior=None, weights=None, freqs=None, taus=None,
+                             of="samples", posterior=True, joint=False, moments=True) -> SkyDistanceLogLike:
+        """:meth:`loglike_sky` marginalised over the amplitude scale of the template as well -> :class:`SkyDistanceLogLike`: the
+        evidence marginal over phase, arrival time, sky position and distance, a sky map that assumes no distance (``post_sky``),
+        a distance posterior that assumes no sky position (``post_dist``) and, per pixel, the conditional mean and spread of
+        ``d / d_ref`` (``dist_mean``, ``dist_std``) that turn the sky map into a volume map.  ``response``, ``delays``,
+        ``log_prior`` (the pixels' log prior mass), ``weights``, ``freqs``, ``taus``, ``of``, padded targets: as in
+        :meth:`loglike_sky`; ``scales`` [n_a] and ``log_prior_scale`` [n_a]: as in :meth:`loglike_distance`
+        (:func:`~npf_gwwaveform_amd.functional.distance_prior` makes both), but ONE grid shared by the tasks.  All are float64
+        device tensors the host never reads.  ``posterior=True``: the two marginal posteriors and their mixtures over the
+        latent samples; ``joint=True``: ``post_joint`` [.., B, P, n_a]; ``moments=True``: ``dist_mean`` / ``dist_std``.  One
+        ``npf_waveform_loglike_sky_dist`` call, four launches in place of ``4 P``; inference only, no host sync, so a ``query``
+        and its ``loglike_sky_distance`` can be captured in one graph (call once at the sizes before capturing) and replayed
+        after the grids and priors were overwritten in place.
+        Out of scope: gradients; per-task or per-pixel scale grids; moments of the mixture over the latent samples; antenna
+        patterns from angles; adaptive pixel refinement; continuous amplitude integration."""
+        if self._y_dim != 2:
+            raise ValueError("loglike_sky_distance needs a model whose two outputs are (amplitude, phase): y_dim == 2, got "
+                             f"{self._y_dim}")
+        if of not in ("samples", "mean"):
+            raise ValueError(f"of must be 'samples' or 'mean', got {of!r}")
+        n_z, B, T = self.batch_shape
+        rows, ld = (n_z * B, 4) if of == "samples" else (B, 2)
+        FN.check_loglike_sky_distance_args((rows, T, ld), data, response, delays, scales, log_prior_scale, log_prior, weights, freqs, taus)
+        with torch.no_grad():
+            h = self._waveform_rows(of, rows, ld)
+            m = FN.waveform_loglike_sky_distance(h, data, response, delays, scales, log_prior_scale, log_prior, weights, freqs, taus,
+                                                 n_valid=self._n_trgt, posterior=posterior, joint=joint, moments=moments)
+            lead, P, n_a = (rows // B, B), response.shape[0], scales.shape[0]
+            tau = m.tau_index.double().mul_(float(taus[1])).add_(float(taus[0])).view(lead) if taus is not None else None
+            per = lambda t, *tail: t.view(*lead, *tail) if t is not None else None  # noqa: E731
+            return SkyDistanceLogLike(m.lnl, m.lnl_vol.view(lead), m.pix_index.view(lead), m.scale_index.view(lead),
+                                      scales.detach()[m.scale_index.view(lead).long()],
+                                      m.tau_index.view(lead) if taus is not None else None, tau, m.snr.view(lead),
+                                      m.scale_hat.view(lead), per(m.post_sky, P), per(m.post_dist, n_a), m.post_sky_mix,
+                                      m.post_dist_mix, per(m.post_joint, P, n_a), per(m.dist_mean, P), per(m.dist_std, P))
 
     def _waveform_rows(self, of, rows, ld):
         """The (amplitude, phase) rows a likelihood is evaluated on: the raw decoder output or the mixture mean."""
